@@ -6,20 +6,26 @@ SFF solver, 1M-node budget (authored step circum=14 / dtree=18: SURVEY.md §8(d)
 
 A "step" is a fixed block of `--waves-per-step` waves of the tree-expansion loop (a wave = `--wave` frontier
 slots, each sampled / neighbour-queried / collision-checked for up to ThresholdMisses rounds, then committed in
-order).  With the defaults (and the driver's `--steps 20 --warmup 5`) the 20 timed steps of 9 waves span the WHOLE
-job: 10 roots -> the 1M-node budget (166 waves of 16384 slots; the CPU oracle's run of exactly this job is pinned in
-tests/golden/full_size_run_w16384.json and the GPU must reproduce it node for node).  The warm-up steps run on a separate, discarded forest of the
-same workload so that the timed region starts from the roots with warm kernels, allocations and caches.
-`value` = accepted node expansions per second over the timed steps, whole job, with the map, the robot and the
-node store resident in HBM before the timed region starts.
+order).  With the defaults the first 19 timed steps of 9 waves span the WHOLE job: 10 roots -> the 1M-node budget
+(166 waves of 16384 slots; the CPU oracle's run of exactly this job is pinned in tests/golden/full_size_run_w16384.json
+and the GPU must reproduce it node for node).  `--steps K` runs exactly K steps: the step in which a job reaches its
+budget ends there, and the next step starts the same job again from the roots on a fresh forest (set up between the
+two steps, outside the timed steps, like the first job's forest).  The warm-up steps run the same way on a separate,
+discarded forest so that the timed region starts from the roots with warm kernels, allocations and caches.
+`value` = accepted node expansions per second over the timed steps, with the map, the robot and the node store
+resident in HBM before the timed region starts; `ms_per_step` = milliseconds per timed step.
 
-Prints ONE JSON line (rank 0): the driver's contract plus
+Prints ONE JSON line (rank 0): the driver's contract plus the library's counters of the timed steps and
   roofline      neighbour-query kernel of the timed region, HIP-event timed inside the library on its launch
                 stream; `traffic` only from a PMC summary collected with exactly these arguments (profiles/)
+`--full` adds what takes runs of its own, after the timed region:
+  quality       planner-quality figures of the whole job at the bench's wave (a run of its own)
   cpu_baseline  the CPU oracle (kind "port": the reference binary cannot be built, RAPID is absent from its
                 tree), wave = 1 == the reference's sequential loop, on a bounded sample of the same workload
   wave_sweep    the same forest at wave = 1 / 64 / 512 (bounded samples) and a quality block that compares
                 the planner's output at small and large waves (the reference loop is wave = 1)
+  sweep_kernel_roofline, extra_legs   the stand-alone linear sweep; SFF*, RRT*, RRT, Multi-T-RRT, priority mode
+`--dump-outputs DIR` writes what the timed path returns after its last step (see dump_outputs) as DIR/<name>.npy.
 `--gpus N` (N > 1) without a torchrun environment re-launches itself under torch.distributed.run.
 """
 import argparse
@@ -58,10 +64,15 @@ def parse_args():
                     help="sharded runs: the library drives the exchange itself (ncclAllGather on its own communicator, "
                          "whole waves enqueued ahead) instead of torch.distributed per round; opt-in until validated on "
                          "a multi-GPU node")
-    ap.add_argument("--cpu-iters", type=int, default=120000, help="iterations of the CPU baseline sample (0 = skip)")
-    ap.add_argument("--no-sweep-micro", action="store_true", help="skip the stand-alone k_sweep roofline measurement")
-    ap.add_argument("--no-wave-sweep", action="store_true", help="skip the wave = 1 / 64 / 512 legs and the quality block")
-    ap.add_argument("--no-extra-legs", action="store_true", help="skip the SFF* (configs[4]) and RRT* legs")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed region, also the quality block, the CPU baseline, the wave sweep, the stand-alone "
+                         "k_sweep roofline and the extra legs (the four below select among them)")
+    ap.add_argument("--cpu-iters", type=int, default=120000, help="--full: iterations of the CPU baseline sample (0 = skip)")
+    ap.add_argument("--no-sweep-micro", action="store_true", help="--full: skip the stand-alone k_sweep roofline measurement")
+    ap.add_argument("--no-wave-sweep", action="store_true", help="--full: skip the wave = 1 / 64 / 512 legs and the quality block")
+    ap.add_argument("--no-extra-legs", action="store_true", help="--full: skip the SFF* (configs[4]) and RRT* legs")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the timed path computed in its last step as DIR/<name>.npy (float64, < 64 MB)")
     return ap.parse_args()
 
 
@@ -120,6 +131,41 @@ def forest_quality(S, forest, ctx, sc):
     return q
 
 
+# counters.npy holds these Forest.stats() entries in this order: the ones that define the result (no timers)
+DUMP_COUNTERS = ("n_nodes", "iterations", "n_trees", "n_connected", "n_borders", "frontier_size", "closed_size", "solved",
+                 "collide_calls", "path_free_calls", "nn_queries", "waves")
+DUMP_NODES = 1 << 19      # node rows written at most (96 bytes each with their index): a seeded sample beyond that
+DUMP_BORDERS = 1 << 17    # border rows written at most (40 bytes each)
+
+
+def dump_outputs(path, forest):
+    """What a caller of the timed path receives from the forest after the last timed step - Forest.nodes(),
+    Forest.borders(), the counters of Forest.stats() that define the result and Forest.fingerprint() - as float64
+    arrays in path/<name>.npy (exact: every integer here is below 2**53; the fingerprint is split into two 32-bit
+    halves).  A forest with more rows than DUMP_NODES / DUMP_BORDERS is written as a fixed, seeded sample of its rows
+    (node_index / border_index name them), so that the files stay below 64 MB."""
+    import numpy as np
+
+    def rows(n, cap, seed):
+        if n <= cap:
+            return np.arange(n)
+        return np.sort(np.random.RandomState(seed).choice(n, cap, replace=False))
+
+    os.makedirs(path, exist_ok=True)
+    st = forest.stats()
+    nd = forest.nodes()
+    bd = forest.borders(cap=max(1, st["n_borders"]))
+    ni = rows(len(nd["parent"]), DUMP_NODES, 1)
+    bi = rows(len(bd["n1"]), DUMP_BORDERS, 2)
+    fp = int(forest.fingerprint())
+    arrays = {"node_index": ni, "border_index": bi, "counters": [st[k] for k in DUMP_COUNTERS],
+              "fingerprint": [fp >> 32, fp & 0xFFFFFFFF]}
+    arrays.update({"node_" + k: v[ni] for k, v in nd.items()})
+    arrays.update({"border_" + k: v[bi] for k, v in bd.items()})
+    for name, a in arrays.items():
+        np.save(os.path.join(path, name + ".npy"), np.asarray(a, dtype=np.float64))
+
+
 def main():
     args = parse_args()
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
@@ -175,52 +221,89 @@ def main():
         torch.cuda.synchronize()
 
     B = max(1, args.waves_per_step)
+
+    def run_steps(forest, n):
+        """n steps of B waves.  The step in which the job reaches its budget ends there; the next step starts the
+        job again from the roots on a fresh forest, created between the two steps (set-up, not a step, like the first
+        job's forest).  Returns the forest of the last step, the steps' times in ms, the seconds spent between steps
+        on set-up, the number of jobs, the first job's starting counters and the counters summed over the jobs."""
+        step_ms, setup_s, jobs, fresh = [], 0.0, 1, True
+        first = job0 = forest.stats()
+        total = dict.fromkeys(first, 0)
+        w = first["waves"]
+        while len(step_ms) < n:
+            ts = time.perf_counter()
+            run_waves(forest, B)
+            dt = time.perf_counter() - ts
+            w1 = forest.stats()["waves"]
+            if w1 > w:
+                step_ms.append(1e3 * dt)
+                fresh = False
+            elif fresh:
+                raise RuntimeError("bench.py: a fresh forest ran no wave (node budget below the roots?)")
+            else:
+                setup_s += dt       # the job had ended with the previous step: no step was run
+            if w1 - w < B and len(step_ms) < n:
+                c0 = time.perf_counter()
+                end = forest.stats()
+                for k in total:
+                    total[k] += end[k] - job0[k]
+                forest.close()
+                forest = make_forest()
+                job0 = forest.stats()
+                w1, fresh = job0["waves"], True
+                jobs += 1
+                setup_s += time.perf_counter() - c0
+            w = w1
+        end = forest.stats()
+        for k in total:
+            total[k] += end[k] - job0[k]
+        return forest, step_ms, setup_s, jobs, first, total
+
     # ---- warm-up: W steps of the same workload on a forest that is then thrown away
     if args.warmup > 0:
-        fw = make_forest()
-        run_waves(fw, args.warmup * B)
+        fw = run_steps(make_forest(), args.warmup)[0]
         fw.close()
 
-    # ---- timed region: exactly K steps (the last one ends early if the node budget is reached inside it)
+    # ---- timed region: exactly K steps
     forest = make_forest()
-    s0 = forest.stats()
-    step_ms = []
     barrier()
     t0 = time.perf_counter()
-    steps_done = 0
-    for _ in range(args.steps):
-        w_before = forest.stats()["waves"]
-        ts = time.perf_counter()
-        run_waves(forest, B)
-        step_ms.append(1e3 * (time.perf_counter() - ts))
-        if forest.stats()["waves"] == w_before:
-            step_ms.pop()
-            break           # the job had already finished: no step was run
-        steps_done += 1
+    forest, step_ms, setup_s, jobs, s0, d = run_steps(forest, args.steps)
+    steps_done = len(step_ms)
     torch.cuda.synchronize()
     t1 = time.perf_counter()
     barrier()
     s1 = forest.stats()
-    elapsed = t1 - t0
+    elapsed = t1 - t0 - setup_s
     if distributed:
         t = torch.tensor([elapsed], dtype=torch.float64, device="cuda")
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
-    acc = float(s1["n_nodes"] - s0["n_nodes"])
-    checks = float(s1["collide_calls"] - s0["collide_calls"])
-    executed = float(s1["poses_executed"] - s0["poses_executed"] + s1["samples_executed"] - s0["samples_executed"])
+    acc = float(d["n_nodes"])
+    checks = float(d["collide_calls"])
+    executed = float(d["poses_executed"] + d["samples_executed"])
     if distributed:  # the forest (nodes, reference-equivalent checks) is shared; executed work is per rank
         t = torch.tensor([executed], dtype=torch.float64, device="cuda")
         dist.all_reduce(t, op=dist.ReduceOp.SUM)
         executed = float(t.item())
-    quality_main = forest_quality(S, forest, ctx, sc) if rank == 0 else None
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, forest)
     forest.close()
+    quality_main = None
+    if args.full:
+        # the planner's output of the whole job at the bench's wave (a run of its own: the timed steps need not end
+        # with a finished job)
+        fq = make_forest()
+        run_waves(fq, 0)
+        quality_main = forest_quality(S, fq, ctx, sc) if rank == 0 else None
+        fq.close()
 
     out = None
     if rank == 0:
-        sweep_ms = s1["sweep_ms"] - s0["sweep_ms"]
-        sweeps = s1["sweeps"] - s0["sweeps"]
-        sweep_nodes = s1["sweep_nodes"] - s0["sweep_nodes"]
+        sweep_ms = d["sweep_ms"]
+        sweeps = d["sweeps"]
+        sweep_nodes = d["sweep_nodes"]
         event_ms = sweep_ms
         # `frac` is priced with the HIP events the contract names (on the library's launch stream, every 32nd wave launched
         # kernel by kernel; ~1.5 us ABOVE the rocprofv3 kernel duration of the same command, profiles/r6_bench_kernel_stats.csv).
@@ -228,8 +311,8 @@ def main():
         # read into one of 64 shards (round 5 sampled every 16th workgroup and so could miss the last one out) - which is
         # first instruction in .. last instruction out, ~2 us BELOW rocprofv3's dispatch begin .. end.  The rocprofv3 average
         # itself is printed when the committed summary was collected with exactly this run's arguments.
-        clock_launches = s1["query_clock_launches"] - s0["query_clock_launches"]
-        clock_ms = (s1["query_clock_ms"] - s0["query_clock_ms"]) if (clock_launches > 0 and clock_launches == sweeps) else None
+        clock_launches = d["query_clock_launches"]
+        clock_ms = d["query_clock_ms"] if (clock_launches > 0 and clock_launches == sweeps) else None
         achieved = (24.0 * sweep_nodes / (sweep_ms * 1e-3)) / 1e9 if sweep_ms > 0 else 0.0
         # HBM-side bytes per launch of the neighbour-query kernel: only from a PMC summary that was collected
         # (separate rocprofv3 --pmc passes, profiles/collect.sh) with exactly the arguments of this run
@@ -264,10 +347,11 @@ def main():
             "config": {
                 "workload": "dense_3D.obj (1832 tris) + robot_cylinder_small (124 tris), 6-DoF, 10 seeded roots, SFF, "
                             "circum=14 dtree=18, 1M-node budget; step = %d waves of %d frontier slots; the timed steps "
-                            "run the whole job from the roots (warm-up on a separate forest)" % (B, args.wave),
+                            "run the job from the roots, a job that reaches the budget is followed by a fresh one (set up "
+                            "between two steps; warm-up on a separate forest)" % (B, args.wave),
                 "wave": args.wave, "waves_per_step": B, "wave_per_gpu": args.wave // world, "node_budget": args.budget,
                 "seed": args.seed, "nodes_at_start": s0["n_nodes"], "nodes_at_end": s1["n_nodes"],
-                "waves": int(s1["waves"] - s0["waves"]),
+                "waves": int(d["waves"]), "jobs": jobs,
                 "parallelism": "1 GPU" if world == 1 else
                 "one forest, wave slots sharded over %d GPUs (i %% world), RCCL all-gather of answer records per round "
                 "(%s)" % (world, "the library's own communicator, whole waves enqueued by the library"
@@ -275,12 +359,12 @@ def main():
             },
             "collision_checks_per_s": checks / elapsed,
             "collision_checks_executed_per_s": executed / elapsed,
-            "iterations": s1["iterations"] - s0["iterations"],
+            "iterations": d["iterations"],
             "step_ms": [round(x, 3) for x in step_ms],
             "time_split_ms": {"total": 1e3 * elapsed, "sweep_kernel": sweep_ms,
-                              "collide_kernels": s1["collide_ms"] - s0["collide_ms"],
-                              "sample_kernel": s1["sample_ms"] - s0["sample_ms"],
-                              "host_logic": s1["host_ms"] - s0["host_ms"]},
+                              "collide_kernels": d["collide_ms"],
+                              "sample_kernel": d["sample_ms"],
+                              "host_logic": d["host_ms"]},
             "roofline": {
                 # neighbour query of one round (grid walk over the node grid and the round's own grid, exact fp64
                 # re-test, classification of the hits: one fused kernel), timed live on the library's launch stream:
@@ -297,21 +381,22 @@ def main():
                 "avg_launch_us_by_rocprofv3": rocprof_us,
                 "own_bytes_GBps": (traffic / (1e-3 * sweep_ms / max(1, sweeps)) / 1e9) if (traffic and sweep_ms > 0) else None,
                 "avg_nodes_per_launch": sweep_nodes / max(1, sweeps),
-                "avg_queries_per_launch": (s1["sweep_queries"] - s0["sweep_queries"]) / max(1, sweeps),
+                "avg_queries_per_launch": d["sweep_queries"] / max(1, sweeps),
             },
-            "quality": {"wave_%d_full_run" % args.wave: quality_main},
         }
-        out["time_split_ms"]["commit_kernels"] = s1["commit_ms"] - s0["commit_ms"]
-        out["time_split_ms"]["graph_launched_waves"] = int(s1["graph_launches"] - s0["graph_launches"])
+        if args.full:
+            out["quality"] = {"wave_%d_full_run" % args.wave: quality_main}
+        out["time_split_ms"]["commit_kernels"] = d["commit_ms"]
+        out["time_split_ms"]["graph_launched_waves"] = int(d["graph_launches"])
         if distributed:
             # what bounds the strong scaling of ONE forest over N GPUs: per round, the part every rank
             # repeats (sampling + the in-order commit), the part that shards (neighbour query + collision: 1/N each) and
             # the exchange (pack + all-gather of the answer records + unpack).  HIP events of this run (rank 0); the
             # per-wave kernels (frontier picks, closed list: replicated too) are not in it.
             rounds = max(1, sweeps)
-            rep = 1e3 * ((s1["sample_ms"] - s0["sample_ms"]) + (s1["commit_ms"] - s0["commit_ms"])) / rounds
-            shd = 1e3 * ((s1["sweep_ms"] - s0["sweep_ms"]) + (s1["collide_ms"] - s0["collide_ms"])) / rounds
-            exc = 1e3 * (s1["exchange_ms"] - s0["exchange_ms"]) / rounds
+            rep = 1e3 * (d["sample_ms"] + d["commit_ms"]) / rounds
+            shd = 1e3 * (d["sweep_ms"] + d["collide_ms"]) / rounds
+            exc = 1e3 * d["exchange_ms"] / rounds
             out["dist_budget_us_per_round"] = {
                 "replicated": rep, "sharded_over_ranks": shd, "pack_gather_unpack": exc, "ranks": world,
                 "amdahl_speedup_bound_at_8_ranks": (rep + shd) / (rep + shd / 8.0 + exc) if rep + shd > 0 else None,
@@ -352,7 +437,7 @@ def main():
                     "modelled_speedup_over_the_one_gpu_job_at_wave_%d" % args.wave: elapsed / (per_rank * rs * 1e-6),
                     "kind": "Amdahl composition of measured ONE-GPU terms (no multi-GPU hardware here); the exchange is the "
                             "one-rank figure - 8 ranks move 8 x the bytes"}
-        if world == 1 and not args.no_sweep_micro:
+        if args.full and world == 1 and not args.no_sweep_micro:
             # the linear k-NN sweep on its own (SURVEY.md 8(d) micro-benchmark, see profiles/sweep_microbench.py): N
             # uniform nodes, ONE query per pass, radius for ~32 neighbours; kernel time from the library's HIP events
             rs = np.random.RandomState(1)
@@ -391,7 +476,7 @@ def main():
                                             "us_per_pass": tt * 1e6, "achieved": 24.0 * Nn / tt / 1e9, "peak": 8000.0,
                                             "unit": "GB/s", "frac": 24.0 * Nn / tt / 8e12, "traffic": sweep_traffic,
                                             "traffic_source": sweep_src}
-        if world == 1 and not args.no_wave_sweep:
+        if args.full and world == 1 and not args.no_wave_sweep:
             # the small-wave end: wave = 1 IS the reference's sequential loop (one sample per GPU round trip)
             legs = {}
 
@@ -445,7 +530,7 @@ def main():
                 f.run()
                 out["quality"]["wave_%d_30k_nodes" % wv] = forest_quality(S, f, ctx, sc)
                 f.close()
-        if world == 1 and not args.no_extra_legs:
+        if args.full and world == 1 and not args.no_extra_legs:
             # the other two solvers north_star names, each with the CPU oracle's sequential loop beside it (bounded samples)
             import oracle_lib as O
             legs = {}
@@ -578,7 +663,7 @@ def main():
                                        "nodes": so["n_nodes"], "seconds": dto, "cores": 1}
             legs["sff_priority"] = pl
             out["extra_legs"] = legs
-        if args.cpu_iters > 0 and world == 1:
+        if args.full and args.cpu_iters > 0 and world == 1:
             import oracle_lib as O
             w = O.World(sc["env"], sc["robot"], O.TRIG_PORTABLE)
             fo = O.Forest(w, roots, sc["limits"], dist_tree=sc["dist_tree"], sampling_dist=sc["sampling_dist"], dim=6,

@@ -25,7 +25,7 @@ for c in FETCH_SIZE WRITE_SIZE; do
 done
 python3 $root/profiles/summarize_pmc.py --kernel-stats $out/${tag}_kernel_stats.csv --bench-args "--steps 20 --warmup 5 $extra" \
   $out/${tag}_pmc_FETCH_SIZE/p_counter_collection.csv $out/${tag}_pmc_WRITE_SIZE/p_counter_collection.csv > $out/${tag}_pmc_summary.json
-cd $root && timeout 600 python3 $BENCH > $out/${tag}_bench_full.log 2>&1
+cd $root && timeout 600 python3 $BENCH --full > $out/${tag}_bench_full.log 2>&1
 tail -1 $out/${tag}_bench_full.log > $out/${tag}_bench_line.json
 rm -rf $out/${tag}_trace/t_kernel_trace.csv $out/${tag}_pmc_FETCH_SIZE $out/${tag}_pmc_WRITE_SIZE
 echo done
