@@ -156,6 +156,7 @@ typedef struct {
   uint64_t spec_steps;       /* waves of one slot, speculated (k_spec_waves): publish -> evaluate -> commit steps ... */
   uint64_t spec_evaluated;   /* ... attempts its workers evaluated (speculation included) ... */
   uint64_t spec_committed;   /* ... and attempts that were committed (= iterations run by that kernel) */
+  uint64_t batch_launches;   /* launches of the batch kernel (sffgpu_forest_run_batch) this forest took part in */
 } sffgpu_forest_stats;
 
 int sffgpu_forest_create(sffgpu_ctx* ctx, const sffgpu_forest_cfg* cfg, const double* roots6, int n_roots,
@@ -163,6 +164,15 @@ int sffgpu_forest_create(sffgpu_ctx* ctx, const sffgpu_forest_cfg* cfg, const do
 void sffgpu_forest_destroy(sffgpu_forest* f);
 /* run to termination, or for at most max_waves waves when max_waves > 0 */
 int sffgpu_forest_run(sffgpu_forest* f, int max_waves);
+/* N independent forests, each of waves of ONE slot (the reference's order), advanced together: one wavefront per forest,
+ * one kernel launch for all of them.  Every forest ends exactly as sffgpu_forest_run(f[i], max_waves) would leave it.
+ * Members: device engine, wave == 1, world == 1, no goal, no priority_bias, at most 64 roots, SFF or SFF* (the two kinds
+ * of one batch go out as two launches); all on one device, each on a context of its own (a context owns one node store).
+ * SFFGPU_ERR_ARG, before anything has run: a member that does not qualify, two members of one context, the same forest
+ * twice, n <= 0, f == NULL.  When a member fails, its error code is returned, *failed is its index (-1 otherwise) and
+ * the message is on ITS context; every other member has been left after a whole number of launches - consistent, and
+ * free to run on, alone or in a batch.  The statistics' total_ms of every member grows by the wall time of the call. */
+int sffgpu_forest_run_batch(sffgpu_forest* const* f, int n, int max_waves, int32_t* failed /* may be NULL */);
 int sffgpu_forest_get_stats(sffgpu_forest* f, sffgpu_forest_stats* out);
 /* nodes in global creation order (Solver::allNodes): any output may be NULL */
 int sffgpu_forest_get_nodes(sffgpu_forest* f, double* pos6, int32_t* parent, int32_t* tree, int32_t* iter,

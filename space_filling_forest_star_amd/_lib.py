@@ -23,6 +23,7 @@ EXPORTED_SYMBOLS = [
     "sffgpu_collide_transforms", "sffgpu_ctx_set_stream", "sffgpu_rccl_unique_id", "sffgpu_ctx_rccl_init", "sffgpu_ctx_set_allgather", "sffgpu_forest_device_engine", "sffgpu_forest_exchange_bytes",
     "sffgpu_forest_rounds_per_wave", "sffgpu_forest_dev_wave_begin", "sffgpu_forest_dev_round_eval",
     "sffgpu_forest_dev_round_commit", "sffgpu_forest_dev_wave_end", "sffgpu_forest_in_wave", "sffgpu_forest_round_begin", "sffgpu_forest_round_records", "sffgpu_forest_round_commit",
+    "sffgpu_forest_run_batch",
 ]
 
 # sffgpu_allgather_fn: int fn(void* user, const void* send_dev, void* recv_dev, size_t words_i32, void* hip_stream)
@@ -58,7 +59,8 @@ class ForestStats(C.Structure):
                 ("mate_overflow_requeries", C.c_uint64), ("star_rounds", C.c_uint64), ("star_passes", C.c_uint64),
                 ("star_members", C.c_uint64), ("star_rewires", C.c_uint64), ("host_fallback_waves", C.c_uint64),
                 ("commit_ms", C.c_double), ("exchange_ms", C.c_double), ("graph_launches", C.c_uint64),
-                ("spec_steps", C.c_uint64), ("spec_evaluated", C.c_uint64), ("spec_committed", C.c_uint64)]
+                ("spec_steps", C.c_uint64), ("spec_evaluated", C.c_uint64), ("spec_committed", C.c_uint64),
+                ("batch_launches", C.c_uint64)]
 
     def as_dict(self):
         return {k: getattr(self, k) for k, _ in self._fields_}
@@ -135,6 +137,8 @@ def lib():
     L.sffgpu_forest_create.argtypes = [C.c_void_p, C.POINTER(ForestCfg), c_dp, C.c_int, C.POINTER(C.c_void_p)]
     L.sffgpu_forest_destroy.argtypes = [C.c_void_p]
     L.sffgpu_forest_run.argtypes = [C.c_void_p, C.c_int]
+    if hasattr(L, "sffgpu_forest_run_batch"):   # (SFFGPU_LIB may name a build from before forest batches; run_batch says so)
+        L.sffgpu_forest_run_batch.argtypes = [C.POINTER(C.c_void_p), C.c_int, C.c_int, c_ip]
     L.sffgpu_forest_get_stats.argtypes = [C.c_void_p, C.POINTER(ForestStats)]
     L.sffgpu_forest_get_nodes.argtypes = [C.c_void_p, c_dp, c_ip, c_ip, c_ip, c_dp, c_dp]
     L.sffgpu_forest_get_borders.argtypes = [C.c_void_p, c_ip, c_ip, c_ip, c_ip, c_dp, C.c_int]
@@ -787,6 +791,28 @@ def _run_distributed_native(forest, max_waves, group):
             allw, counts = exchange_records(rec, group)
             forest.round_commit(allw, counts)
     return forest.stats()["waves"] - w0
+
+
+def run_batch(forests, max_waves=0):
+    """Advance independent forests of waves of ONE slot together (sffgpu_forest_run_batch): one wavefront per forest, one
+    kernel launch for all of them; each forest ends exactly as its own run(max_waves) would leave it.  Every forest
+    lives on a context of its own, all on one device.  An error names the member it came from."""
+    forests = list(forests)
+    L = lib()
+    if not hasattr(L, "sffgpu_forest_run_batch"):
+        raise SffGpuError("this build of libsffgpu.so has no sffgpu_forest_run_batch")
+    arr = (C.c_void_p * max(1, len(forests)))(*[f.h for f in forests])
+    failed = C.c_int32(-1)
+    rc = L.sffgpu_forest_run_batch(arr if forests else None, len(forests), max_waves, C.byref(failed))
+    if rc < 0:
+        msg = "sffgpu error %d" % rc
+        if 0 <= failed.value < len(forests):
+            ctx = forests[failed.value].ctx
+            msg += " (member %d): %s" % (failed.value, L.sffgpu_last_error(ctx.h).decode())
+        elif rc == -1:
+            msg += ": not a batch (needs n >= 1 forests with wave == 1, world == 1, the device engine, no goal, no priority_bias," \
+                   " at most 64 roots, each on a context of its own, all on one device)"
+        raise SffGpuError(msg)
 
 
 def run_distributed(forest, max_waves=0, group=None):

@@ -3,6 +3,7 @@
 #include <cstdlib>
 #include <cstring>
 #include <string>
+#include <vector>
 
 #include "engine.h"
 
@@ -159,6 +160,33 @@ int sffgpu_forest_run(sffgpu_forest* f, int max_waves) {
     return SFFGPU_ERR_HIP;
   }
   return f->f->need_host_exchange ? SFFGPU_NEED_HOST_EXCHANGE : SFFGPU_OK;
+}
+int sffgpu_forest_run_batch(sffgpu_forest* const* f, int n, int max_waves, int32_t* failed) {
+  if (failed) *failed = -1;
+  if (!f || n <= 0) return SFFGPU_ERR_ARG;
+  std::vector<Forest*> members((size_t)n);
+  for (int i = 0; i < n; ++i) {
+    if (!f[i] || !f[i]->f->batch_eligible() || f[i]->f->ctx->device != f[0]->f->ctx->device) return SFFGPU_ERR_ARG;
+    for (int j = 0; j < i; ++j)   // (a context owns ONE node store: two members of one context - or one forest twice - would share it)
+      if (f[j] == f[i] || f[j]->f->ctx == f[i]->f->ctx) return SFFGPU_ERR_ARG;
+    members[(size_t)i] = f[i]->f;
+  }
+  int bad = -1;
+  auto blame = [&](const std::string& msg) {
+    if (bad < 0 || bad >= n) bad = 0;
+    f[bad]->owner->c->err = msg;
+    if (failed) *failed = bad;
+  };
+  try {
+    run_forest_batch(members.data(), n, max_waves, &bad);
+  } catch (const HipError& e) {
+    blame(e.msg);
+    return SFFGPU_ERR_HIP;
+  } catch (const std::exception& e) {
+    blame(e.what());
+    return SFFGPU_ERR_STATE;
+  }
+  return SFFGPU_OK;
 }
 int sffgpu_rccl_unique_id(uint8_t id128[128]) {
   if (!id128) return SFFGPU_ERR_ARG;

@@ -379,6 +379,12 @@ struct Forest {
   void run_device(int max_waves);
   bool seq_eligible() const;        // waves of one slot, plain SFF: the persistent single-wavefront loop (k_seq_waves)
   void run_device_seq(int max_waves);
+  // one launch of that loop in two halves (run_device_seq, and run_forest_batch below, which launches many forests at once)
+  int seq_launch_waves(int waves_left) const;     // waves the next launch may run (waves_left: the caller's bound, 0 = none)
+  uint64_t seq_words_end(int batch) const;         // ... and the ring position its engine words have to reach
+  sffk::SeqArgs seq_prepare(int batch);            // tops the ring up to there, builds the kernel's arguments
+  void seq_lists_fault();                          // SFFK_FAULT_LISTS came back: that wave on the host-replay engine, state back up
+  bool batch_eligible() const;                     // may be a member of run_forest_batch
   bool spec_setup();                // the speculative kernel's scenario tree and buffers; false = k_seq_waves runs the loop
   bool seq_suspended = false;
   bool test_exchange_self = false;  // SFFGPU_TEST_EXCHANGE_SELF (read when the forest is created): a one-rank forest packs / unpacks its records too
@@ -510,6 +516,13 @@ struct Forest {
   void run(int max_waves);
   uint64_t fingerprint() const;
 };
+
+// Forest batches (forest_batch.cpp): n independent forests of waves of ONE slot, each on a context of its own, advanced in
+// lock step - one wavefront per forest, one launch of k_seq_waves_batch per kind (SFF / SFF*) for all of them - until each
+// has terminated or run max_waves waves (0 = no bound).  The caller has checked the members (batch_eligible, distinct
+// contexts, one device).  A member that throws ends the call: *failed = its index, the exception goes on to the caller;
+// every other member has been taken in after a whole number of launches.
+void run_forest_batch(Forest* const* members, int n, int max_waves, int* failed);
 
 struct RNode {
   double pos[6];

@@ -1387,6 +1387,71 @@ bool Forest::spec_setup() {
 // waves of ONE slot (the reference's own order): k_seq_waves runs whole outer iterations back to back inside one launch,
 // thousands of waves per launch; the host tops the engine-word ring up between launches and handles what the round engine's
 // host side handles (growth, re-celling, a list overflow -> that wave is finished on the host-replay engine)
+// ---- the two halves of one launch of the single-wavefront loop, shared by run_device_seq (one forest) and run_forest_batch
+// (forest_batch.cpp: many forests in lock step).  Prepare: how many waves the launch may run, the engine words they may
+// need, the kernel's arguments.  Take in: dev_finish_wave on the status block that came back, then seq_lists_fault.
+int Forest::seq_launch_waves(int waves_left) const {
+  const uint64_t per_wave = (uint64_t)(8 + std::max(1, cfg.threshold_misses) * (cfg.dim == 2 ? 1 : 6));
+  int batch = (int)std::min<uint64_t>(4096, dev.ring_words / (2 * per_wave));
+  if (waves_left > 0) batch = std::min(batch, waves_left);
+  return batch;
+}
+
+uint64_t Forest::seq_words_end(int batch) const {   // the ring has to hold the words up to this absolute position
+  const uint64_t per_wave = (uint64_t)(8 + std::max(1, cfg.threshold_misses) * (cfg.dim == 2 ? 1 : 6));
+  return dev.last.cursor + (uint64_t)batch * per_wave + 16;
+}
+
+sffk::SeqArgs Forest::seq_prepare(int batch) {
+  Ctx& c = *ctx;
+  DevEngine& d = dev;
+  dev_ring_top_up(d.last.cursor, seq_words_end(batch) - d.last.cursor);
+  sffk::SeqArgs a{};
+  a.f = dev_view();
+  a.st = sffk::NodeStoreMut{c.sx.as<float>(), c.sy.as<float>(), c.sz.as<float>(), c.syaw.as<float>(),
+                            c.spitch.as<float>(), c.sroll.as<float>(), c.stree.as<int32_t>(), c.spos.as<double>()};
+  a.g = c.gridv;
+  a.env = c.envv;
+  a.rob = c.robv;
+  memcpy(a.limits, cfg.limits, sizeof a.limits);
+  a.dist_tree = cfg.dist_tree;
+  a.sampling_dist = cfg.sampling_dist;
+  a.sweep_abs_eps = c.sweep_eps();
+  a.trig = (cfg.libm_sampling || d.dev_trig) ? d.trig.as<double>() : nullptr;
+  a.words_end = d.produced;
+  a.grid_ovf_src = c.gridv.ovf_cnt;
+  a.dim = cfg.dim;
+  a.max_waves = batch;
+  a.hit_cap = hit_cap;
+  a.grid_ovf_limit = c.grid_rebuild_at();
+  a.optimize = cfg.optimize ? 1 : 0;
+  if (cfg.optimize) {
+    const sffk::StarView sv = star_view();
+    a.ktab = sv.ktab;
+    a.tree_cnt = sv.tree_cnt;
+    a.hist = sv.hist;
+    a.hist_ctl = sv.hist_ctl;
+    a.hist_cap = sv.hist_cap;
+    a.cell_edge = c.grid_cell;
+    a.knn_slack = 8 * c.sweep_eps();
+  }
+  return a;
+}
+
+// a bounded device list ran over inside the loop: the faulted wave is finished on the host-replay engine (unbounded lists)
+// and the state goes back to the device
+void Forest::seq_lists_fault() {
+  ++st.host_fallback_waves;
+  dev_to_host();
+  while (in_wave) {
+    round_begin();
+    int32_t cnt = (int32_t)records.size();
+    round_commit(records.data(), cnt, &cnt, 1);
+  }
+  on_list_fault();
+  dev_upload_state();
+}
+
 void Forest::run_device_seq(int max_waves) {
   Ctx& c = *ctx;
   DevEngine& d = dev;
@@ -1395,7 +1460,6 @@ void Forest::run_device_seq(int max_waves) {
   double wait_ms = 0;
   if (!d.active) dev_upload_state();
   const uint64_t w0 = d.last.waves;
-  const uint64_t per_wave = (uint64_t)(8 + std::max(1, cfg.threshold_misses) * (cfg.dim == 2 ? 1 : 6));
   while (true) {
     const sffk::DevCtrl& k = d.last;
     if (!k.in_wave && k.terminated) break;
@@ -1410,41 +1474,11 @@ void Forest::run_device_seq(int max_waves) {
       wait_ms = 0;
       continue;
     }
-    int batch = (int)std::min<uint64_t>(4096, d.ring_words / (2 * per_wave));
-    if (max_waves > 0) batch = std::min(batch, max_waves - (int)(k.waves - w0));
-    dev_ring_top_up(k.cursor, (uint64_t)batch * per_wave + 16);
+    const int batch = seq_launch_waves(max_waves > 0 ? max_waves - (int)(k.waves - w0) : 0);
+    sffk::SeqArgs a = seq_prepare(batch);
     if (d.ring_pending) {
       HIPCHK(hipStreamWaitEvent(c.stream, d.ev_ring, 0));
       d.ring_pending = false;
-    }
-    sffk::SeqArgs a{};
-    a.f = dev_view();
-    a.st = sffk::NodeStoreMut{c.sx.as<float>(), c.sy.as<float>(), c.sz.as<float>(), c.syaw.as<float>(),
-                              c.spitch.as<float>(), c.sroll.as<float>(), c.stree.as<int32_t>(), c.spos.as<double>()};
-    a.g = c.gridv;
-    a.env = c.envv;
-    a.rob = c.robv;
-    memcpy(a.limits, cfg.limits, sizeof a.limits);
-    a.dist_tree = cfg.dist_tree;
-    a.sampling_dist = cfg.sampling_dist;
-    a.sweep_abs_eps = c.sweep_eps();
-    a.trig = (cfg.libm_sampling || d.dev_trig) ? d.trig.as<double>() : nullptr;
-    a.words_end = d.produced;
-    a.grid_ovf_src = c.gridv.ovf_cnt;
-    a.dim = cfg.dim;
-    a.max_waves = batch;
-    a.hit_cap = hit_cap;
-    a.grid_ovf_limit = c.grid_rebuild_at();
-    a.optimize = cfg.optimize ? 1 : 0;
-    if (cfg.optimize) {
-      const sffk::StarView sv = star_view();
-      a.ktab = sv.ktab;
-      a.tree_cnt = sv.tree_cnt;
-      a.hist = sv.hist;
-      a.hist_ctl = sv.hist_ctl;
-      a.hist_cap = sv.hist_cap;
-      a.cell_edge = c.grid_cell;
-      a.knn_slack = 8 * c.sweep_eps();
     }
     const char* trace_path = getenv("SFFGPU_SEQ_TRACE");
     DevBuf trace_buf;
@@ -1515,17 +1549,7 @@ void Forest::run_device_seq(int max_waves) {
         fprintf(stderr, "\n");
       }
     }
-    if (fault == SFFK_FAULT_LISTS) {
-      ++st.host_fallback_waves;
-      dev_to_host();
-      while (in_wave) {
-        round_begin();
-        int32_t cnt = (int32_t)records.size();
-        round_commit(records.data(), cnt, &cnt, 1);
-      }
-      on_list_fault();
-      dev_upload_state();
-    }
+    if (fault == SFFK_FAULT_LISTS) seq_lists_fault();
   }
   st.total_ms += ms_since(t0);
   st.host_ms += ms_since(t0) - wait_ms;

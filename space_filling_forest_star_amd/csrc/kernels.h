@@ -648,6 +648,10 @@ struct SeqArgs {
   int32_t* trace; int trace_cap;
 };
 void launch_seq_waves(hipStream_t s, const SeqArgs& a);
+// Forest batches (k_seq_waves_batch): n independent forests in one launch, workgroup b = one wavefront = members_dev[b]'s
+// loop.  All members of a launch are of one kind (optimize: SFF*), lds = the largest collide_lds_bytes(rob.n_tri, 1) among
+// them.  Returns the first error of setting the kernel's attribute or of the launch itself.
+hipError_t launch_seq_waves_batch(hipStream_t s, const SeqArgs* members_dev, int n, bool optimize, size_t lds);
 // ---- the same loop, SPECULATED over many wavefronts (round 6, k_spec_waves).  One wavefront computes an attempt in
 // ~10-15 us however idle the other 1 023 SIMDs are; but what an attempt of the NEXT waves will be is known in advance
 // up to one small unknown per wave - which of its ThresholdMisses attempts, if any, is accepted (src/forest.h:138-178: the

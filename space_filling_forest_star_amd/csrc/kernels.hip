@@ -4458,411 +4458,39 @@ __device__ __attribute__((noinline)) void sq_knn(const GridView& g, const double
   if (dbg && lane == 0) { atomicAdd(dbg, d_sh); atomicAdd(dbg + 1, d_cg); atomicAdd(dbg + 2, d_ob); atomicAdd(dbg + 3, d_in); atomicAdd(dbg + 4, 1ULL); atomicAdd(dbg + 5, (unsigned long long)no); }
 }
 
+// the loop itself is seq_waves_body.inc.  k_seq_waves includes it as text, on its by-value argument, which keeps this entry's
+// code as it was before the loop was shared; seq_waves_body is the same loop as a function of a reference (k_seq_waves_batch)
 template <bool OPT>
 __global__ __launch_bounds__(64) void k_seq_waves(SeqArgs A) {
-  extern __shared__ double lds_d[];
-  __shared__ int32_t s_fh, s_ovf;
-  __shared__ int32_t h_id[64], h_tree[64];
-  __shared__ double h_d[64], h_pos[64 * 6];
-  const DevForestView& f = A.f;
-  DevCtrl* c = f.ctrl;
-  const int lane = threadIdx.x;
-  if (c->halt || c->in_wave) return;            // (a wave the host left half done goes through the round engine)
-  double* rtri = lds_d;
-  double* stage = rtri + (size_t)A.rob.n_tri * 9;
-  int32_t* ibase = reinterpret_cast<int32_t*>(stage + STAGE_DOUBLES);
-  int32_t* stack = ibase;                        // (+ the triangle-grid hash set behind it)
-  int32_t* cand = ibase + (STACK_CAP + TG_HASH);
-  int32_t* queue = cand + CAND_CAP;
-  for (int i = lane; i < A.rob.n_tri * 9; i += 64) rtri[i] = A.rob.tri[i];
-  __builtin_amdgcn_wave_barrier();
-  fill_robot_boxes(rtri, reinterpret_cast<double*>(queue + QUEUE_CAP), A.rob.n_tri, lane, 64);
-  __builtin_amdgcn_wave_barrier();
-  // ---- the control block, in registers (everything here is the same in every lane)
-  int n_nodes = c->n_nodes, iter = c->iter, fn = c->frontier_n, cn = c->closed_n, nb = c->n_borders;
-  int solved = c->solved, empty_frontier = c->empty_frontier, terminated = c->terminated;
-  const int front_sel = c->front_sel;
-  unsigned long long cursor = c->cursor, cc = c->collide_calls, pf = c->path_free_calls, nq = c->nn_queries;
-  unsigned long long ex_pose = c->poses_executed, ex_seg = c->segments_executed, ex_smp = c->samples_executed;
-  unsigned long long waves = c->waves, rounds = c->rounds, rnodes = c->round_nodes, rqueries = c->round_queries, redraws = 0;
-  int32_t* frontier = front_sel ? f.frontier2 : f.frontier;
-  const int TM = f.threshold_misses, WP = f.words_per, R = f.n_trees;
-  int fault = 0, w_round = 0, w_node = 0, w_pos = 0, w_closed = 0, in_wave = 0;
-  unsigned long long st_rounds = 0, st_members = 0, st_rewires = 0;
-  // phase clocks (10 ns ticks): pick + node, sample, pose, parent edge, neighbour query, neighbour loop, append, wave end
-  uint64_t pre_w[6] = {0, 0, 0, 0, 0, 0};
-  unsigned long long pre_at = ~0ULL;
-  const bool clk = A.f.profile != 0;   // (a clock read is a scalar memory round trip)
-  unsigned long long ph[8] = {0, 0, 0, 0, 0, 0, 0, 0}, tq = clk ? wall_clock64() : 0ULL;
-  auto lap = [&](int k) { if (!clk) return; const unsigned long long t = wall_clock64(); ph[k] += t - tq; tq = t; };
-  for (int wv = 0; wv < A.max_waves && !terminated && !fault; ++wv) {
-    // ---- what the round engine checks before a round (round_begin_scalars), and what this launch has to leave to the host
-    if (n_nodes + 1 > f.node_cap - 8 || nb + TM > f.border_cap) { fault = SFFK_FAULT_CAPACITY; break; }
-    if ((unsigned long long)(nb + TM) * 2ULL > f.bt_mask + 1ULL) { fault = SFFK_FAULT_BORDER_TABLE; break; }
-    if (cursor + 8ULL + (unsigned long long)(TM * WP) > A.words_end) break;      // out of engine words: the host tops the ring up
-    if (sq_i32(A.grid_ovf_src) > A.grid_ovf_limit) break;                         // the grid wants to re-cell itself
-    // ---- node selection (src/forest.h:136-151)
-    const int use_closed = cn > 0 && empty_frontier;
-    const int pool = use_closed ? cn : fn;
-    if (pool < 1) { terminated = 1; break; }
-    int pick;
-    do { pick = sq_lemire(f.ring[cursor & f.ring_mask], (unsigned long long)pool); ++cursor; if (pick < 0) ++redraws; } while (pick < 0);
-    const int node = sq_i32((use_closed ? f.closed : frontier) + pick);
-    ++waves;
-    double cpos[6];
-    for (int k = 0; k < 6; ++k) cpos[k] = sq_f64(A.st.pos + 6 * (size_t)node + k);
-    const int mine = sq_i32(A.st.tree + node);
-    const double droot_ex = sq_f64(f.d_root + node);
-    const bool force = (sq_u8(f.nflag + node) & 1) != 0;
-    bool failing = true;
-    w_node = node; w_pos = pick; w_closed = use_closed;
-    lap(0);
-    for (int rd = 0; rd < TM && failing && iter < f.max_iterations; ++rd) {
-      // (attempt-start snapshot: a fault rolls exactly this attempt back)
-      const int iter_a = iter;
-      const unsigned long long cur_a = cursor, cc_a = cc, pf_a = pf, nq_a = nq, xp_a = ex_pose, xs_a = ex_seg, xm_a = ex_smp;
-      bool flt = false;
-      // (the words of this attempt were asked for while the previous one ran, whenever the stream position was the
-      // expected one; the next attempt's are asked for now)
-      uint64_t w[6];
-      if (pre_at == cursor) { for (int k = 0; k < 6; ++k) w[k] = pre_w[k]; }
-      else { for (int k = 0; k < 6; ++k) w[k] = k < WP ? f.ring[(cursor + k) & f.ring_mask] : 0ULL; }
-      pre_at = cursor + (unsigned long long)WP;
-      for (int k = 0; k < 6; ++k) pre_w[k] = k < WP ? f.ring[(pre_at + k) & f.ring_mask] : 0ULL;
-      SampleTrig ht{};
-      if (A.trig) {
-        const double* t0 = A.trig + 3 * (size_t)(cursor & f.ring_mask);
-        ht.c_phi = t0[0]; ht.s_phi = t0[1];
-        if (WP == 6) {
-          const double* t1 = A.trig + 3 * (size_t)((cursor + 1) & f.ring_mask);
-          const double* t3 = A.trig + 3 * (size_t)((cursor + 3) & f.ring_mask);
-          ht.c_theta = t1[0]; ht.s_theta = t1[1]; ht.acos_u = t3[2];
-        }
-      }
-      cursor += (unsigned long long)WP;
-      ++iter;
-      ++rounds; rnodes += (unsigned long long)(n_nodes + 1); ++rqueries;
-      double qp[6];
-      if (!A.trig) {
-        // the five transcendental values of the sample, two at a time: lanes 0 / 1 evaluate the same function on phi / theta
-        // (one instruction stream whatever the lane count; the same portable routines, so the same bits as sample_point)
-        const double ang = sample_angle(lane == 1 ? w[1] : w[0]);
-        const double sv = sffp::psin(ang), cv = sffp::pcos(ang);
-        ht.s_phi = __shfl(sv, 0); ht.c_phi = __shfl(cv, 0);
-        ht.s_theta = __shfl(sv, 1); ht.c_theta = __shfl(cv, 1);
-        ht.acos_u = WP == 6 ? sffp::pacos(sample_acos_arg(w[3])) : 0.0;
-      }
-      const bool ok = sample_point_with(w, cpos, A.sampling_dist, A.dim, A.limits, qp, ht);
-      lap(1);
-      if (!ok) continue;                                           // :246 !result
-      // ---- Environment::Collide(newPoint)
-      cc += 1; ex_pose += 1;
-      bool hit = false;
-      if (A.env.n_tri != 0 && !surely_clear(A.env, qp)) {
-        double Rm[9], c3[3];
-        if (qp[3] == 0 && qp[4] == 0 && qp[5] == 0) { Rm[0] = Rm[4] = Rm[8] = 1; Rm[1] = Rm[2] = Rm[3] = Rm[5] = Rm[6] = Rm[7] = 0; }
-        else rotation(qp, Rm);
-        xform(Rm, qp, A.rob.center, c3);
-        hit = pose_exact(A.env, A.rob, rtri, stack, cand, stage, qp, Rm, c3, lane);
-      }
-      lap(2);
-      if (hit) continue;
-      // ---- isPathFree(expanded, newPoint)
-      pf += 1; ex_seg += 1;
-      const bool free0 = (sq_edge_clear_fast(A.env, cpos, qp, lane, cc, ex_smp) || sq_path_free(A.env, A.rob, rtri, stack, cand, queue, stage, cpos, qp, &s_fh, &s_ovf, lane, cc, ex_smp, flt));
-      bool reject = !free0;
-      lap(3);
-      const double pdist = dist6(cpos, qp);                        // parentDistance, :250
-      int n_hit = 0;
-      if (!flt && !reject) {
-        nq += (unsigned long long)R;                               // :262-267 one radiusSearch per tree
-        // ---- the neighbours: exact 6-D ball of radius max(parentDistance, treeDistance) from the cells its box touches
-        const double r = pdist > A.dist_tree ? pdist : A.dist_tree;
-        const double ri = (r + A.sweep_abs_eps) * (1.0 + 1e-5);
-        const float rf = sqrtf((float)(ri * ri) * 1.000001f) * 1.000001f;
-        const GridView& g = A.g;
-        const float qx = (float)qp[0], qy = (float)qp[1], qz = (float)qp[2];
-        const int lx = grid_coord(qx - rf, g.ox, g.inv_cell, g.nx), hx = grid_coord(qx + rf, g.ox, g.inv_cell, g.nx);
-        const int ly = grid_coord(qy - rf, g.oy, g.inv_cell, g.ny), hy = grid_coord(qy + rf, g.oy, g.inv_cell, g.ny);
-        const int lz = grid_coord(qz - rf, g.oz, g.inv_cell, g.nz), hz = grid_coord(qz + rf, g.oz, g.inv_cell, g.nz);
-        const int wx = hx - lx + 1, wy = hy - ly + 1, wz = hz - lz + 1;
-        const int total = wx * wy * wz;
-        auto take = [&](bool valid, const GridItem* src) {        // one candidate per lane -> the hit list in LDS
-          bool h = false;
-          double d = 0, p6[6];
-          int id = 0, tr = 0;
-          if (valid) {
-            const unsigned long long* q8 = reinterpret_cast<const unsigned long long*>(src);
-            for (int k = 0; k < 6; ++k) p6[k] = __longlong_as_double((long long)sq_u64(q8 + k));
-            const unsigned long long it = sq_u64(q8 + 6);
-            id = (int)(unsigned)(it & 0xffffffffULL); tr = (int)(unsigned)(it >> 32);
-            d = dist6(p6, qp);
-            h = d < r;
-          }
-          const unsigned long long hm = __ballot(h);
-          if (h) {
-            const int at = n_hit + __popcll(hm & ((1ULL << lane) - 1ULL));
-            if (at < 64) { h_id[at] = id; h_tree[at] = tr; h_d[at] = d; for (int k = 0; k < 6; ++k) h_pos[6 * at + k] = p6[k]; }
-          }
-          n_hit += __popcll(hm);
-        };
-        for (int c0 = 0; c0 < total; c0 += 64) {
-          const int ci = c0 + lane;
-          int cell = 0, m = 0;
-          if (ci < total) {
-            const int q1 = ci / wx, q2 = q1 / wy;
-            cell = ((lz + q2) * g.ny + (ly + q1 - q2 * wy)) * g.nx + (lx + ci - q1 * wx);
-            m = sq_i32(g.cnt + cell);
-            if (m > g.bk) m = g.bk;
-          }
-          int inc = m;
-          for (int off = 1; off < 64; off <<= 1) {
-            const int o = __shfl_up(inc, off);
-            if (lane >= off) inc += o;
-          }
-          const int tot = __shfl(inc, 63);
-          for (int base = 0; base < tot; base += 64) {
-            const int j = base + lane;
-            const int jj = j < tot ? j : tot - 1;
-            int lo = 0, hi = 63;
-            while (lo < hi) {
-              const int mid = (lo + hi) >> 1;
-              if (__shfl(inc, mid) > jj) hi = mid; else lo = mid + 1;
-            }
-            const int src_cell = __shfl(cell, lo);
-            const int slot = jj - (__shfl(inc, lo) - __shfl(m, lo));
-            take(j < tot, g.items + (size_t)src_cell * g.bk + slot);
-          }
-        }
-        int no = sq_i32(g.ovf_cnt);
-        if (no > g.ovf_cap) no = g.ovf_cap;
-        for (int base = 0; base < no; base += 64) take(base + lane < no, g.ovf + base + lane);
-        if (n_hit > A.hit_cap || n_hit > 64) flt = true;
-      }
-      lap(4);
-      if (!flt && !reject) {
-        // ---- the neighbour loop (:270-300) in the reference's order: tree id, then distance, then id; an edge is only
-        // checked when the loop reaches it
-        __builtin_amdgcn_wave_barrier();
-        const bool have = lane < n_hit;
-        const int id = have ? h_id[lane] : 0x7fffffff;
-        const int t = have ? h_tree[lane] : 0x7fffffff;
-        const double d = have ? h_d[lane] : 0.0;
-        const bool same = t == mine;
-        const bool qk = have && (same ? (!force && d < pdist - SFFG_TOL) : (d < A.dist_tree - SFFG_TOL));   // :276 / :283
-        int rank = 0;
-        for (int j = 0; j < n_hit; ++j) {
-          const int tj = __shfl(t, j), idj = __shfl(id, j), qj = __shfl((int)qk, j);
-          const double dj = __shfl(d, j);
-          if (qj && (tj < t || (tj == t && (dj < d || (dj == d && idj < id))))) ++rank;
-        }
-        const int n_q = __popcll(__ballot(qk));
-        for (int rk = 0; rk < n_q && !reject && !flt; ++rk) {
-          const unsigned long long sel = __ballot(qk && rank == rk);
-          const int src = __ffsll((long long)sel) - 1;
-          const int s_same = __shfl((int)same, src), s_id = __shfl(id, src), s_tree = __shfl(t, src);
-          double np6[6];
-          for (int k = 0; k < 6; ++k) np6[k] = h_pos[6 * src + k];
-          pf += 1; ex_seg += 1;
-          if (s_same) {
-            const bool fr = (sq_edge_clear_fast(A.env, np6, qp, lane, cc, ex_smp) || sq_path_free(A.env, A.rob, rtri, stack, cand, queue, stage, np6, qp, &s_fh, &s_ovf, lane, cc, ex_smp, flt));
-            if (fr) reject = true;                                 // :276-280 overcrowded
-          } else {
-            const bool fr = (sq_edge_clear_fast(A.env, cpos, np6, lane, cc, ex_smp) || sq_path_free(A.env, A.rob, rtri, stack, cand, queue, stage, cpos, np6, &s_fh, &s_ovf, lane, cc, ex_smp, flt));
-            if (fr && !flt) {                                      // :288-294 border entry unless the pair has one
-              const int a = s_id < node ? s_id : node, b = s_id < node ? node : s_id;
-              const unsigned long long key = ((unsigned long long)(uint32_t)a << 32) | ((unsigned long long)(uint32_t)b + 1ULL);
-              size_t h = (size_t)((key * 0x9E3779B97F4A7C15ULL) >> 17) & (size_t)f.bt_mask;
-              bool fresh = false;
-              for (int guard = 0; guard < (1 << 24); ++guard) {
-                const unsigned long long cur = sq_u64(f.bt_key + h);
-                if (cur == key) { fresh = sq_u64(f.bt_val + h) == ~0ULL; break; }
-                if (cur == 0ULL) { fresh = true; break; }
-                h = (h + 1) & (size_t)f.bt_mask;
-              }
-              if (fresh) {
-                if (lane == 0) {
-                  f.bt_key[h] = key;
-                  f.bt_val[h] = c->epoch << 32;
-                  f.b_n1[nb] = a; f.b_n2[nb] = b;
-                  f.b_ta[nb] = s_tree < mine ? s_tree : mine; f.b_tb[nb] = s_tree < mine ? mine : s_tree;
-                  f.b_dist[nb] = sq_f64(f.d_root + s_id) + droot_ex + dist6(np6, cpos);
-                  f.pair[(size_t)s_tree * R + mine] = 1;
-                  f.pair[(size_t)mine * R + s_tree] = 1;
-                }
-                sq_drain();
-                ++nb;
-              }
-            }
-            reject = true;                                         // :296-299
-          }
-        }
-      }
-      lap(5);
-      if (flt) {
-        // a bounded list overflowed (hits, triangle candidates): this attempt never happened - the host finishes the wave
-        iter = iter_a; cursor = cur_a; cc = cc_a; pf = pf_a; nq = nq_a; ex_pose = xp_a; ex_seg = xs_a; ex_smp = xm_a;
-        --rounds; rnodes -= (unsigned long long)(n_nodes + 1); --rqueries;
-        fault = SFFK_FAULT_LISTS; w_round = rd; in_wave = 1;
-        break;
-      }
-      if (reject) continue;
-      // ---- SFF* (:307-351): the k nearest of the tree, choose parent, (the node), rewire - each edge checked when its turn comes
-      int par_new = node;
-      double dcl_new = pdist, best = pdist + droot_ex;
-      TopK mt{1.0e300, 0x7fffffff};
-      int n_mem = 0;
-      double m_droot = 0;
-      if (OPT) {
-        const int k = __popcll(__ballot(lane > 0 && lane <= SFFK_STAR_KMAX + 1 && A.ktab[lane] <= n_nodes));   // (size_t)(2e log10 N), :309
-        if (k > SFFK_STAR_KMAX) flt = true;
-        else {
-          nq += 1;                                                                          // :317 knnSearch
-          sq_knn(A.g, qp, mine, k, sq_i32(A.tree_cnt + 16 * mine), A.cell_edge, A.knn_slack, lane, mt, n_mem);
-          if (lane < n_mem) m_droot = sq_f64(f.d_root + mt.id);
-          for (int m = 0; m < n_mem && !flt; ++m) {                                         // :320-327
-            const double nd = __shfl(mt.d, m) + __shfl(m_droot, m);
-            if (nd < best - SFFG_TOL) {
-              const int idm = __shfl(mt.id, m);
-              double mp[6];
-              for (int q = 0; q < 6; ++q) mp[q] = sq_f64(A.st.pos + 6 * (size_t)idm + q);
-              pf += 1; ex_seg += 1;
-              if ((sq_edge_clear_fast(A.env, qp, mp, lane, cc, ex_smp) || sq_path_free(A.env, A.rob, rtri, stack, cand, queue, stage, qp, mp, &s_fh, &s_ovf, lane, cc, ex_smp, flt)) && !flt) {
-                best = nd; par_new = idm; dcl_new = __shfl(mt.d, m);
-              }
-            }
-          }
-        }
-        if (flt) {
-          iter = iter_a; cursor = cur_a; cc = cc_a; pf = pf_a; nq = nq_a; ex_pose = xp_a; ex_seg = xs_a; ex_smp = xm_a;
-          --rounds; rnodes -= (unsigned long long)(n_nodes + 1); --rqueries;
-          fault = SFFK_FAULT_LISTS; w_round = rd; in_wave = 1;
-          break;
-        }
-      }
-      // ---- the new node (:329, :353-367)
-      const int idn = n_nodes;
-      if (lane == 0) {
-        const size_t o = (size_t)idn;
-        A.st.x[o] = (float)qp[0]; A.st.y[o] = (float)qp[1]; A.st.z[o] = (float)qp[2];
-        A.st.yaw[o] = (float)qp[3]; A.st.pitch[o] = (float)qp[4]; A.st.roll[o] = (float)qp[5];
-        for (int k = 0; k < 6; ++k) A.st.pos[6 * o + k] = qp[k];
-        A.st.tree[o] = mine;
-        f.parent[o] = par_new;
-        f.d_closest[o] = dcl_new;
-        f.d_root[o] = best;
-        f.iter[o] = (uint32_t)iter;
-        f.nflag[o] = 2;
-        frontier[fn] = idn;
-        if (OPT) {
-          atomicAdd(A.tree_cnt + 16 * mine, 1);
-          if (A.hist) {
-            const int at = atomicAdd(A.hist_ctl, 1);
-            if (at < A.hist_cap) { A.hist[3 * (size_t)at] = idn; A.hist[3 * (size_t)at + 1] = par_new; A.hist[3 * (size_t)at + 2] = iter; }
-            else A.hist_ctl[1] = 1;
-          }
-        }
-        GridItem it;
-        for (int k = 0; k < 6; ++k) it.p[k] = qp[k];
-        it.id = idn; it.tree = mine; it.pad[0] = it.pad[1] = 0;
-        grid_put(A.g, it);
-      }
-      sq_drain();
-      ++n_nodes; ++fn;
-      failing = false;
-      if (OPT) {
-        // rewire (:332-350): a member the new node's cost improves, if the edge member -> new is free
-        ++st_rounds; st_members += (unsigned long long)n_mem;
-        for (int m = 0; m < n_mem; ++m) {
-          const double dm = __shfl(mt.d, m), drm = __shfl(m_droot, m);
-          const double proposed = best + dm;
-          if (proposed < drm - SFFG_TOL) {
-            const int idm = __shfl(mt.id, m);
-            double mp[6];
-            for (int q = 0; q < 6; ++q) mp[q] = sq_f64(A.st.pos + 6 * (size_t)idm + q);
-            pf += 1; ex_seg += 1;
-            bool f2 = false;
-            const bool fr = (sq_edge_clear_fast(A.env, mp, qp, lane, cc, ex_smp) || sq_path_free(A.env, A.rob, rtri, stack, cand, queue, stage, mp, qp, &s_fh, &s_ovf, lane, cc, ex_smp, f2));
-            if (fr) {
-              if (lane == 0) {
-                f.parent[idm] = idn; f.d_closest[idm] = dm; f.d_root[idm] = proposed;
-                if (A.hist) {
-                  const int at = atomicAdd(A.hist_ctl, 1);
-                  if (at < A.hist_cap) { A.hist[3 * (size_t)at] = idm; A.hist[3 * (size_t)at + 1] = idn; A.hist[3 * (size_t)at + 2] = iter; }
-                  else A.hist_ctl[1] = 1;
-                }
-              }
-              ++st_rewires;
-            }
-          }
-        }
-        sq_drain();
-      }
-      lap(6);
-    }
-    if (fault) break;
-    // ---- the slot is exhausted: its node leaves the frontier for the closed list (:160-178; the erase keeps the order)
-    if (failing && !use_closed) {
-      const int fl = sq_u8(f.nflag + node);
-      if (fl & 2) {
-        if (lane == 0) { f.nflag[node] = (uint8_t)((fl & ~2) | 1); f.closed[cn] = node; }
-        ++cn;
-        for (int j0 = pick; j0 < fn - 1; j0 += 256) {
-          int v[4];
-#pragma unroll
-          for (int u = 0; u < 4; ++u) { const int j = j0 + 64 * u + lane; v[u] = j < fn - 1 ? sq_i32(frontier + j + 1) : 0; }
-#pragma unroll
-          for (int u = 0; u < 4; ++u) { const int j = j0 + 64 * u + lane; if (j < fn - 1) frontier[j] = v[u]; }
-          sq_drain();
-        }
-        --fn;
-      }
-    }
-    sq_drain();
-    // ---- termination (:184-201)
-    empty_frontier = fn == 0 ? 1 : 0;
-    if (!solved && empty_frontier) {
-      // maxConnected() == numRoots: every tree reachable from tree 0 over pairs that hold a border (R <= 64: a lane per tree)
-      unsigned long long reach = 1ULL, frontier_set = 1ULL;
-      if (R <= 64) {
-        unsigned long long row = 0ULL;   // lane a: bit b = pair (a, b) has a border
-        if (lane < R) for (int b2 = 0; b2 < R; ++b2) if (sq_u8(f.pair + (size_t)lane * R + b2)) row |= 1ULL << b2;
-        while (frontier_set) {
-          const int a = __ffsll((long long)frontier_set) - 1;
-          frontier_set &= frontier_set - 1;
-          const unsigned long long ra = __shfl(row, a) & ~reach;
-          reach |= ra; frontier_set |= ra;
-        }
-        solved = __popcll(reach) == R ? 1 : 0;
-      } else fault = SFFK_FAULT_LISTS;   // (more trees than lanes: the round engine's serial walk)
-    }
-    const bool budget = f.node_budget > 0 && n_nodes >= f.node_budget;
-    terminated = (solved || iter >= f.max_iterations || budget) ? 1 : 0;
-    if (A.trace && wv < A.trace_cap && lane == 0) {
-      int32_t* t = A.trace + 8 * (size_t)wv;
-      t[0] = node; t[1] = pick; t[2] = iter; t[3] = (int32_t)(cursor & 0x7fffffffULL); t[4] = failing ? TM : 0; t[5] = n_nodes; t[6] = fn; t[7] = cn;
-    }
-    lap(7);
+#include "seq_waves_body.inc"
+}
+
+template <bool OPT>
+__device__ __forceinline__ void seq_waves_body(const SeqArgs& A) {
+#include "seq_waves_body.inc"
+}
+
+// Forest batches: workgroup b (one wavefront) runs the loop of members[b], an independent forest with a store, a grid, a
+// ring and a control block of its own.  The member's arguments are read through the uniform pointer, never copied into a
+// local, so they live in scalar registers like the kernel arguments of k_seq_waves do.  A workgroup never waits for another
+// one - no step word, no records, no barrier across the grid - so, unlike k_spec_waves, no grid size can strand a workgroup:
+// what is not resident at once simply runs when a slot frees up.
+template <bool OPT>
+__global__ __launch_bounds__(64) void k_seq_waves_batch(const SeqArgs* __restrict__ members, int n) {
+  if ((int)blockIdx.x >= n) return;
+  seq_waves_body<OPT>(members[blockIdx.x]);
+}
+
+hipError_t launch_seq_waves_batch(hipStream_t s, const SeqArgs* members_dev, int n, bool optimize, size_t lds) {
+  if (n <= 0) return hipSuccess;
+  const void* fn = optimize ? reinterpret_cast<const void*>(k_seq_waves_batch<true>) : reinterpret_cast<const void*>(k_seq_waves_batch<false>);
+  if (lds > 48 * 1024) {
+    const hipError_t e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    if (e != hipSuccess) return e;
   }
-  if (lane == 0) {
-    for (int k = 0; k < 8; ++k) c->wprof[k] += ph[k];
-    c->n_nodes = n_nodes; c->iter = iter; c->frontier_n = fn; c->closed_n = cn; c->n_borders = nb;
-    c->solved = solved; c->empty_frontier = empty_frontier; c->terminated = terminated;
-    c->cursor = cursor; c->collide_calls = cc; c->path_free_calls = pf; c->nn_queries = nq;
-    c->poses_executed = ex_pose; c->segments_executed = ex_seg; c->samples_executed = ex_smp;
-    c->waves = waves; c->rounds = rounds; c->round_nodes = rnodes; c->round_queries = rqueries;
-    c->redraws += (int)redraws;
-    c->star_rounds += st_rounds; c->star_passes += st_rounds; c->star_members += st_members; c->star_rewires += st_rewires;
-    c->n_act = 0; c->app_n = 0; c->compact_from = 0;
-    c->grid_ovf = sq_i32(A.grid_ovf_src); c->tgrid_ovf = 0;
-    c->fault = fault;
-    c->halt = (terminated || fault) ? 1 : 0;
-    c->in_wave = in_wave;
-    if (in_wave) {   // the state the host engine resumes the wave from: its one slot, still failing, w_round rounds done
-      c->round = w_round; c->n_slots = 1; c->use_closed = w_closed; c->act_sel = 0; c->act_cnt = 1;
-      f.slot_node[0] = w_node; f.slot_pos[0] = w_pos; f.act_slot[0] = 0;
-    } else c->round = 0;
-  }
+  if (optimize) hipLaunchKernelGGL(k_seq_waves_batch<true>, dim3(n), dim3(64), lds, s, members_dev, n);
+  else hipLaunchKernelGGL(k_seq_waves_batch<false>, dim3(n), dim3(64), lds, s, members_dev, n);
+  return hipGetLastError();
 }
 
 void launch_seq_waves(hipStream_t s, const SeqArgs& a) {
