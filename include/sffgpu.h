@@ -157,6 +157,8 @@ typedef struct {
   uint64_t spec_evaluated;   /* ... attempts its workers evaluated (speculation included) ... */
   uint64_t spec_committed;   /* ... and attempts that were committed (= iterations run by that kernel) */
   uint64_t batch_launches;   /* launches of the batch kernel (sffgpu_forest_run_batch) this forest took part in */
+  uint64_t prio_seq_waves;   /* priority-frontier mode on the device engine: waves whose picks k_prio_begin made one after
+                                the other (SFFGPU_PRIO_SEQ=1) instead of from k_prio_plan's plan */
 } sffgpu_forest_stats;
 
 int sffgpu_forest_create(sffgpu_ctx* ctx, const sffgpu_forest_cfg* cfg, const double* roots6, int n_roots,

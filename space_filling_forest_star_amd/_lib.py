@@ -60,7 +60,7 @@ class ForestStats(C.Structure):
                 ("star_members", C.c_uint64), ("star_rewires", C.c_uint64), ("host_fallback_waves", C.c_uint64),
                 ("commit_ms", C.c_double), ("exchange_ms", C.c_double), ("graph_launches", C.c_uint64),
                 ("spec_steps", C.c_uint64), ("spec_evaluated", C.c_uint64), ("spec_committed", C.c_uint64),
-                ("batch_launches", C.c_uint64)]
+                ("batch_launches", C.c_uint64), ("prio_seq_waves", C.c_uint64)]
 
     def as_dict(self):
         return {k: getattr(self, k) for k, _ in self._fields_}

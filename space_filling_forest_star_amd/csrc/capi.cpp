@@ -97,7 +97,7 @@ int sffgpu_sample_steer(sffgpu_ctx* ctx, const uint64_t* words, const double* ce
 
 int sffgpu_nodes_reset(sffgpu_ctx* ctx, int capacity) {
   if (!ctx || capacity < 0) return SFFGPU_ERR_ARG;
-  GUARD(ctx, ctx->c->store_reset(capacity));
+  GUARD(ctx, { ctx->c->kn = Knobs::from_env(); ctx->c->store_reset(capacity); });
 }
 int sffgpu_nodes_append(sffgpu_ctx* ctx, const double* pos6, const int32_t* tree_id, int n) {
   if (!ctx || n < 0 || (n > 0 && (!pos6 || !tree_id))) return SFFGPU_ERR_ARG;
@@ -107,6 +107,7 @@ int sffgpu_nodes_index(sffgpu_ctx* ctx, const double limits[6], double cell) {
   if (!ctx || !limits || !(cell > 0)) return SFFGPU_ERR_ARG;
   GUARD(ctx, {
     Ctx& c = *ctx->c;
+    c.kn = Knobs::from_env();
     c.grid_bk = 8;
     c.grid_cell0 = cell;
     c.grid_rebuilds = 0;
@@ -147,7 +148,7 @@ int sffgpu_forest_create(sffgpu_ctx* ctx, const sffgpu_forest_cfg* cfg, const do
 }
 void sffgpu_forest_destroy(sffgpu_forest* f) {
   if (!f) return;
-  sff::forest_profile_dump();
+  if (f->f->kn.profile) sff::forest_profile_dump();
   delete f->f;
   delete f;
 }
@@ -478,11 +479,11 @@ int sffgpu_forest_dev_wave_begin(sffgpu_forest* f, int32_t* done) {
 int sffgpu_forest_dev_round_eval(sffgpu_forest* f, void* send_dev) {
   if (!f) return SFFGPU_ERR_ARG;
   // (SFFGPU_TEST_EXCHANGE_SELF: a one-rank forest packs and unpacks too - bench.py --force-dist prices the exchange with it)
-  GUARD(f->owner, f->f->dev_enqueue_round_eval((f->f->cfg.world > 1 || f->f->test_exchange_self) ? send_dev : nullptr));
+  GUARD(f->owner, f->f->dev_enqueue_round_eval((f->f->cfg.world > 1 || f->f->kn.test_exchange_self) ? send_dev : nullptr));
 }
 int sffgpu_forest_dev_round_commit(sffgpu_forest* f, const void* recv_dev) {
   if (!f) return SFFGPU_ERR_ARG;
-  GUARD(f->owner, f->f->dev_enqueue_round_commit((f->f->cfg.world > 1 || f->f->test_exchange_self) ? recv_dev : nullptr));
+  GUARD(f->owner, f->f->dev_enqueue_round_commit((f->f->cfg.world > 1 || f->f->kn.test_exchange_self) ? recv_dev : nullptr));
 }
 int sffgpu_forest_dev_wave_end(sffgpu_forest* f, int32_t* fault) {
   if (!f || !fault) return SFFGPU_ERR_ARG;

@@ -718,8 +718,7 @@ void launch_star_stage(hipStream_t s, const ResolveArgs& a, int n_bound, const S
   const int sample_blocks = (n_bound + 3) / 4;
   int R0 = (int)std::ceil(L.cube_reach / L.cell_edge);
   R0 = R0 < 2 ? 2 : (R0 > STAR_R0_MAX ? STAR_R0_MAX : R0);
-  static const bool lone = getenv("SFFGPU_STAR_KNN") && !strcmp(getenv("SFFGPU_STAR_KNN"), "lone");
-  if (lone) hipLaunchKernelGGL(k_star_knn, dim3(sample_blocks), dim3(256), 0, s, a, L.g, L.tg, L.st, L.cell_edge, L.slack, R0);
+  if (L.knn_lone) hipLaunchKernelGGL(k_star_knn, dim3(sample_blocks), dim3(256), 0, s, a, L.g, L.tg, L.st, L.cell_edge, L.slack, R0);
   else launch_star_knn_wg(s, a, L.g, L.tg, L.st, L.cell_edge, L.slack, n_bound, R0);
   const int event_blocks = (n_bound + 255) / 256;
   // the passes after the first: one launch (k_star_tail, as many passes as the round needs, up to SFFK_STAR_TAIL_PASSES) or -
@@ -727,7 +726,7 @@ void launch_star_stage(hipStream_t s, const ResolveArgs& a, int n_bound, const S
   if (L.tail) {
     const int passes = L.passes > 0 ? L.passes : SFFK_STAR_TAIL_PASSES;
     hipLaunchKernelGGL(k_star_pass, dim3(sample_blocks + event_blocks), dim3(256), 0, s, a, L.env, L.st, 0, sample_blocks);
-    if (passes > 1) launch_star_exact(s, L.env, L.rob, L.st.pos, a.S, 0);
+    if (passes > 1) launch_star_exact(s, L.env, L.rob, L.st.pos, a.S, 0, L.seg_blocks);
     launch_star_tail(s, a, L.env, L.rob, L.st, n_bound, passes, L.tail_wgs, L.tail_stall);
     hipLaunchKernelGGL(k_star_apply, dim3(sample_blocks), dim3(256), 0, s, a, L.tg, n_bound, passes, 1);
     return;
@@ -736,7 +735,7 @@ void launch_star_stage(hipStream_t s, const ResolveArgs& a, int n_bound, const S
   for (int pass = 0; pass < passes; ++pass) {
     hipLaunchKernelGGL(k_star_pass, dim3(sample_blocks + event_blocks), dim3(256), 0, s, a, L.env, L.st, pass, sample_blocks);
     // (what the pass could not answer from the clearance bits; nothing to do = the launch returns at once)
-    if (pass + 1 < passes) launch_star_exact(s, L.env, L.rob, L.st.pos, a.S, pass);
+    if (pass + 1 < passes) launch_star_exact(s, L.env, L.rob, L.st.pos, a.S, pass, L.seg_blocks);
   }
   hipLaunchKernelGGL(k_star_apply, dim3(sample_blocks), dim3(256), 0, s, a, L.tg, n_bound, passes, 0);
 }

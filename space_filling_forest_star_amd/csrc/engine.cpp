@@ -134,7 +134,7 @@ int Mt64::uniform_int(int lo, int hi) {
 
 // ------------------------------------------------------------------ context
 Ctx::Ctx(int dev) : device(dev) {
-  if (const char* e = getenv("SFFGPU_TIMER_STRIDE")) timer_stride = std::max(1, atoi(e));
+  kn = Knobs::from_env();
   int n = 0;
   HIPCHK(hipGetDeviceCount(&n));
   if (n <= 0) throw HipError{"no HIP device visible: libsffgpu has no CPU fallback"};
@@ -312,6 +312,7 @@ static inline uint64_t spread21(uint64_t v) {
 // triangles are ordered along a Morton curve of their box centres, 64 consecutive triangles
 // form a level-0 group, 64 consecutive groups a level-1 group, and so on until <= 64 remain.
 void Ctx::upload_mesh(int role, const double* tri9, int n) {
+  kn = Knobs::from_env();
   HIPCHK(hipSetDevice(device));
   if (role == SFFGPU_MESH_ROBOT) {
     if (n <= 0) throw HipError{"robot mesh must have at least one triangle"};
@@ -468,7 +469,7 @@ void Ctx::build_robot_extents() {
   env_cand.ensure(rec.size() * sizeof(double));
   HIPCHK(hipMemcpy(env_cand.p, rec.data(), rec.size() * sizeof(double), hipMemcpyHostToDevice));
   envv.cand = env_cand.as<double>();
-  if (const char* e = getenv("SFFGPU_NO_CAND")) if (atoi(e)) envv.cand = nullptr;   // (A/B: the four-array gather)
+  if (kn.no_cand) envv.cand = nullptr;   // (A/B: the four-array gather)
 }
 
 // Clearance bits over the environment box (kernels.h, EnvView): one bit per cell, set when a robot whose
@@ -479,19 +480,15 @@ void Ctx::build_clearance() {
   envv.clear_bits_edge = nullptr;
   clear_cells = 0;
   if (!have_env || !have_robot || envv.n_tri <= 0) return;
-  if (const char* e = getenv("SFFGPU_NO_CLEARANCE")) if (atoi(e)) return;
+  if (kn.no_clearance) return;
   // radius about the model origin: the bounding sphere (centre c, radius r) in any rotation stays inside |c| + r
   const double rr = robv.radius + std::sqrt(robv.center[0] * robv.center[0] + robv.center[1] * robv.center[1] +
                                             robv.center[2] * robv.center[2]) * (1 + 1e-9);
   double ext[3], vol_ext = 0;
   for (int a = 0; a < 3; ++a) { ext[a] = env_hi[a] - env_lo[a]; vol_ext = std::max(vol_ext, ext[a]); }
   if (!(vol_ext > 0) || !(rr >= 0)) return;
-  double cap = 134217728.0;
-  if (const char* e = getenv("SFFGPU_CLEAR_CELLS")) cap = std::max(512.0, atof(e));
-  cap = std::min(cap, std::max(32768.0, 4e10 / (double)std::max(1, envv.level_count[0])));
-  double hdiv = 2.0;
-  if (const char* e = getenv("SFFGPU_CLEAR_HDIV")) hdiv = std::max(0.5, atof(e));
-  double h = std::max(rr / hdiv, vol_ext * 1e-4);
+  const double cap = std::min(kn.clear_cells, std::max(32768.0, 4e10 / (double)std::max(1, envv.level_count[0])));
+  double h = std::max(rr / kn.clear_hdiv, vol_ext * 1e-4);
   int n[3];
   double thr = 0, lin_slack = 0;
   const double reach = 0.4 * (1 + 1e-6);
@@ -542,13 +539,13 @@ void Ctx::build_clearance() {
   const auto t_build = std::chrono::steady_clock::now();
   sffk::launch_clear_build(stream, envv, P, env_clear.as<uint32_t>(), env_clear_edge.as<uint32_t>(), cells);
   HIPCHK(hipStreamSynchronize(stream));
-  if (getenv("SFFGPU_PROFILE"))
+  if (kn.profile)
     fprintf(stderr, "[sffgpu clearance bits] both planes built in %.2f ms\n",
             std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_build).count());
   envv.clear_bits = env_clear.as<uint32_t>();
   envv.clear_bits_edge = env_clear_edge.as<uint32_t>();
   clear_cells = cells;
-  if (getenv("SFFGPU_PROFILE")) {   // share of blocked cells per plane
+  if (kn.profile) {   // share of blocked cells per plane
     std::vector<uint32_t> w((size_t)(padded / 32));
     long long blocked[2] = {0, 0};
     for (int pl = 0; pl < 2; ++pl) {
@@ -567,7 +564,7 @@ void Ctx::build_tri_grid() {
   envv.tg_start = nullptr;
   envv.tg_list = nullptr;
   if (!have_env || !have_robot || envv.n_tri <= 0 || envv.n_levels < 1) return;
-  if (const char* e = getenv("SFFGPU_NO_TRIGRID")) if (atoi(e)) return;
+  if (kn.no_trigrid) return;
   double rext = 0, ext = 0;
   for (int a = 0; a < 3; ++a) {
     rext = std::max(rext, robv.hi[a] - robv.lo[a]);
@@ -575,8 +572,7 @@ void Ctx::build_tri_grid() {
   }
   rext = std::max(rext, 2 * robv.radius);
   if (!(ext > 0)) return;
-  double div = 3.0;
-  if (const char* e = getenv("SFFGPU_TG_DIV")) div = std::max(1.0, atof(e));
+  const double div = kn.tg_div;
   const double h = std::max((rext + 6.4) / div, ext / (div > 3.0 ? 256.0 : 128.0));
   long long cells = 1;
   for (int a = 0; a < 3; ++a) {
@@ -696,7 +692,7 @@ void Ctx::grid_setup(const double limits[6], double cell) {
   const size_t ncells = (size_t)gridv.nx * gridv.ny * gridv.nz;
   if (gridv_ovf_cap_next < 65536) gridv_ovf_cap_next = 65536;
   gridv.ovf_cap = gridv_ovf_cap_next;
-  if (const char* e = getenv("SFFGPU_TEST_GRID_OVF")) gridv.ovf_cap = std::max(gridv.ovf_cap / 65536 * atoi(e), atoi(e));  // tests: tiny list
+  if (kn.test_grid_ovf >= 0) gridv.ovf_cap = std::max(gridv.ovf_cap / 65536 * kn.test_grid_ovf, kn.test_grid_ovf);  // tests: tiny list
   g_cnt.ensure(ncells * sizeof(int32_t));
   g_items.ensure(ncells * gridv.bk * sizeof(sffk::GridItem));
   g_ovfcnt.ensure(16);
@@ -755,7 +751,7 @@ void Ctx::grid_check(bool bulk) {
       const size_t cells_now = (size_t)gridv.nx * gridv.ny * gridv.nz;
       double cell = grid_cell;
       if (cells_now * 4 <= 16777216 && grid_cell * 0.63 >= 0.5 * grid_cell0) cell = grid_cell * 0.63;
-      else if (grid_bk < grid_bk_max() && cells_now * (size_t)grid_bk * 2 * sizeof(sffk::GridItem) <= ((size_t)24 << 30)) grid_bk *= 2;
+      else if (grid_bk < kn.test_grid_bkmax && cells_now * (size_t)grid_bk * 2 * sizeof(sffk::GridItem) <= ((size_t)24 << 30)) grid_bk *= 2;
       else if (cells_now * 4 <= 16777216) cell = grid_cell * 0.63;
       else grid_grow_list();
       double lim[6];
@@ -777,7 +773,7 @@ void Ctx::grid_check(bool bulk) {
   const size_t cells_now = (size_t)gridv.nx * gridv.ny * gridv.nz;
   double cell = grid_cell;
   if (cells_now * 4 <= 16777216 && grid_cell * 0.63 >= 0.5 * grid_cell0) cell = grid_cell * 0.63;   // ~4x the cells
-  else if (grid_bk < grid_bk_max() && cells_now * (size_t)grid_bk * 2 * sizeof(sffk::GridItem) <= ((size_t)24 << 30))
+  else if (grid_bk < kn.test_grid_bkmax && cells_now * (size_t)grid_bk * 2 * sizeof(sffk::GridItem) <= ((size_t)24 << 30))
     grid_bk *= 2;                                           // cell count exhausted: deeper buckets (HBM is plentiful) ...
   else grid_grow_list();                                    // ... and only then a longer list
   double lim[6];
@@ -871,7 +867,7 @@ void Ctx::collide_segments_core(const double* a6, const double* b6, const int32_
   r_items2.ensure(((size_t)list_cap + (1u << 20)) * 8);   // (+ one window of the exact kernel, see mask_slot)
   time_begin(T_COLLIDE);
   sffk::launch_seg_prepare(stream, d_a.as<double>(), d_b.as<double>(), n, d_ns, d_fh, d_ov);
-  sffk::launch_collide_segments_dyn(stream, envv, robv, d_a.as<double>(), d_b.as<double>(), d_ns, n, d_ctrl,
+  sffk::launch_collide_segments_dyn(stream, kn, envv, robv, d_a.as<double>(), d_b.as<double>(), d_ns, n, d_ctrl,
                                     r_items.p, list_cap, r_items2.p, d_fh, d_ov);
   time_end();
   HIPCHK(hipMemcpyAsync(h_c.p, d_c.p, (size_t)n * 12, hipMemcpyDeviceToHost, stream));
@@ -971,7 +967,7 @@ void Ctx::seg_refs_begin(int which, const int32_t* ida, const int32_t* idb, int 
   const int list_cap = 8 * n + 65536;
   time_begin(T_COLLIDE);
   sffk::launch_seg_prepare(stream, J.a.as<double>(), J.b.as<double>(), n, d_ns, d_fh, d_ov);
-  sffk::launch_collide_segments_dyn(stream, envv, robv, J.a.as<double>(), J.b.as<double>(), d_ns, n, d_ctrl, r_items.p, list_cap, r_items2.p, d_fh, d_ov);
+  sffk::launch_collide_segments_dyn(stream, kn, envv, robv, J.a.as<double>(), J.b.as<double>(), d_ns, n, d_ctrl, r_items.p, list_cap, r_items2.p, d_fh, d_ov);
   time_end();
   HIPCHK(hipMemcpyAsync(J.hc.p, J.c.p, (size_t)n * 12, hipMemcpyDeviceToHost, stream));
   HIPCHK(hipEventRecord(J.ev, stream));
@@ -1044,7 +1040,7 @@ static void rr_enqueue(Ctx& c, char* db, const RrLayout& L, int row0, int n, int
   if (parts & 1) {
   c.time_begin(T_COLLIDE);
   // (the poses ride the edge kernels: the cull pass marks the ones that need the exact test, the exact kernel takes them first)
-  sffk::launch_round_collide(c.stream, c.envv, c.robv, r_np, n, nullptr, d_hit, c.rr_a.as<double>(), r_np, d_ns, n, d_ctrl, c.r_items.p, list_cap,
+  sffk::launch_round_collide(c.stream, c.kn, c.envv, c.robv, r_np, n, nullptr, d_hit, c.rr_a.as<double>(), r_np, d_ns, n, d_ctrl, c.r_items.p, list_cap,
                              c.r_items2.p, d_fh, d_ov, nullptr);
   c.time_end();
   if (mates) sffk::launch_rrt_mates(c.stream, c.rr_q1.as<sffk::KnnQuery>(), reinterpret_cast<double*>(db + L.o_nd), 2, r_np, d_hit, d_fh, d_ov, n,
@@ -1141,7 +1137,7 @@ void Ctx::rrt_chain(const double* rnd6, const int32_t* tree, int n, double dist,
                          kc ? reinterpret_cast<int32_t*>(db + L1.o_cc) : nullptr);
   // the k nearest and the other trees' nodes of the new points need nothing of the pose / edge answers: they run on a second
   // stream beside them (RRT*: the k-nearest kernel is the longest of the chain)
-  const bool fork = rr_fork && (kmax > 0 || kc) && copy_stream;
+  const bool fork = kn.rrt_fork && (kmax > 0 || kc) && copy_stream;
   if (fork) {
     if (!rr_ev[0]) for (hipEvent_t& e : rr_ev) HIPCHK(hipEventCreateWithFlags(&e, hipEventDisableTiming));
     HIPCHK(hipEventRecord(rr_ev[0], stream));

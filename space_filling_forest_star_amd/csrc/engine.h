@@ -13,6 +13,7 @@
 
 #include "../../include/sffgpu.h"
 #include "kernels.h"
+#include "knobs.h"
 
 namespace sff {
 
@@ -69,6 +70,7 @@ enum TimerKind { T_SWEEP = 0, T_COLLIDE = 1, T_SAMPLE = 2, T_COMMIT = 3, T_EXCHA
 
 struct Ctx {
   int device = 0;
+  Knobs kn;                                   // the environment as it was at the last creation entry (knobs.h says which)
   int wall_clock_khz = 100000;                // rate of wall_clock64() on this device
   hipStream_t stream = nullptr;
   hipStream_t own_stream = nullptr;           // the stream the context created (stream may be replaced by the caller's)
@@ -131,7 +133,6 @@ struct Ctx {
   bool grid_exhausted = false;
   int grid_rebuild_at() const { return grid_exhausted ? std::max(128, gridv.ovf_cap / 4) : std::min(gridv.ovf_cap / 4, 128); }
   void grid_grow_list();
-  static int grid_bk_max() { const char* e = getenv("SFFGPU_TEST_GRID_BKMAX"); return e ? std::max(1, std::min(64, atoi(e))) : 64; }   // (tests: shallow buckets)
   double grid_cell0 = 0;    // the cell edge the forest asked for (re-celling never goes below half of it: a query's
                             // cell count grows with the cube of the ratio)
   int tgrid_ovf_min = 0;    // lower bound of the round grid's overflow list (one wave of samples)
@@ -152,14 +153,12 @@ struct Ctx {
   double kernel_ms[T_KINDS] = {0, 0, 0, 0, 0};
   uint64_t kernel_launches[T_KINDS] = {0, 0, 0, 0, 0};   // timed launches
   uint64_t kernel_calls[T_KINDS] = {0, 0, 0, 0, 0};      // all launches
-  // the forest engine's rounds are sampled (every timer_stride-th is bracketed): their sum is scaled to all rounds,
+  // the forest engine's rounds are sampled (every kn.timer_stride-th is bracketed): their sum is scaled to all rounds,
   // the always-timed batch calls are added as measured
   double round_ms[T_KINDS] = {0, 0, 0, 0, 0};
   uint64_t round_calls[T_KINDS] = {0, 0, 0, 0, 0}, round_timed[T_KINDS] = {0, 0, 0, 0, 0};
   bool round_scope = false;
   bool timing_on = true, timed_now = true;
-  int timer_stride = 32;   // (SFFGPU_TIMER_STRIDE; an eagerly launched, event-bracketed wave costs ~0.25 ms more than its graph
-                           // replay and its HIP events read ~4 us long per kernel: 8 -> 32 is + 2-3 % on the headline job)
   double kernel_ms_total(int kind) const;
 
   explicit Ctx(int dev);
@@ -230,7 +229,6 @@ struct Ctx {
   void seg_finish(const int32_t* hn_in, int n, const double* a6, const double* b6, const void* dev_a, const void* dev_b, uint8_t* is_free,
                   int32_t* first_hit, int32_t* n_samples);
   hipEvent_t rr_ev[3] = {nullptr, nullptr, nullptr};   // rrt_chain: fork after each steer, join before the copy back
-  bool rr_fork = true;                                  // SFFGPU_RRT_FORK=0: the chain's queries on the one stream
   PinBuf rr_hq, rr_hout;
   double sweep_eps() const;
   // one sweep launch over the first n_store entries; per-query hit lists sorted by (dist, id)
@@ -298,8 +296,6 @@ struct DevEngine {
   bool table_dirty = false, ring_pending = false;
   DevBuf frontier2, rm_words, rm_pref, slot_pos, act_slot2, w_acc, acc_pref, ustate32, wg_pub, commit_seq, kc_trace;
   DevBuf ord_hist, ord_start, ord_key, ord_rank, ord_pos, ord_lst, ord_cnt;
-  bool ord_enabled = true;
-  int ord_min_wave = 4096;   // (SFFGPU_ORDER_MIN_WAVE, read when the forest is created)
   DevBuf w_ev, ev_h, ev_nb, ev_raw;   // border events of a round, entered by the append launch (sffk::DevForestView)   // spatial order of a wave's slots (sffk::OrderView)
   DevBuf ctrl, parent, d_root, d_closest, iter, nflag, frontier, closed, claim, slot_node, slot_fail, act_slot, b_n1,
       b_n2, b_ta, b_tb, b_dist, bt_key, bt_val, pair, ring, ulist, d_parent, d_parent2, d_force, fault_pending;
@@ -317,7 +313,7 @@ struct DevEngine {
   // so it is re-captured whenever the signature of those arguments (buffer addresses, sizes, grid geometry) changes.
   hipGraphExec_t wave_graph = nullptr;
   uint64_t wave_graph_sig = 0;
-  bool graph_enabled = true;
+  bool graph_enabled = true;         // (Knobs::no_graph, or a profiler is loaded: the Forest constructor)
   int round_parity = 0;              // which set of sample arrays the round being enqueued uses (fused append + sampling)
   int force_timing = -1;             // >= 0: dev_enqueue_round_eval takes this instead of the per-round stride
   bool round_timing = false;         // the timing decision of the round being enqueued (evaluation -> commit)
@@ -333,23 +329,21 @@ struct DevEngine {
   uint64_t rounds_enqueued = 0;
   int host_nodes = 0, host_borders = 0;   // how much of the device arrays the host mirror holds
   sffk::DevCtrl last{};         // status block after the last completed wave
-  bool zc_status = true;        // the wave's last kernel writes the status block into the pinned ring itself (sffk::status_publish)
   uint32_t status_next = 0;     // sequence number the next published block will carry
   uint32_t status_of[2] = {0, 0};   // ... and the ones the two enqueued waves' blocks carry
-  bool status_copied[2] = {true, true};   // the slot's block came by a copy into h_ctrl[slot] (k_seq_waves, SFFGPU_NO_ZC_STATUS)
+  bool status_copied[2] = {true, true};   // the slot's block came by a copy into h_ctrl[slot] (k_seq_waves, SFFGPU_NO_ZC_STATUS) instead of
+                                          // being written into the pinned ring by the wave's last kernel (sffk::status_publish)
   // waves of one slot, speculated (k_spec_waves): scenario tree, control blocks, records (sffk::SpecArgs)
   DevBuf spec_tab, spec_area;
   DevBuf qclk_sh;               // the query kernel's clock bracket, 64 shards (sffk::DevForestView::qclk_sh)
   int spec_n_sc = 0, spec_sets = 0, spec_tm = 0;
   bool spec_off = false;        // SFFGPU_SPEC=0, or a launch stalled (its workgroups were not resident together)
-  int spec_depth = 0 /* 0 = 3 (the tree), SFF*: 4 (the chain) */, spec_sets_want = 1, spec_test_stall = 0;   // (SFFGPU_SPEC_DEPTH / _SETS / SFFGPU_TEST_SPEC_STALL, read when the forest is created)
-  bool dev_trig_off = false;
-  bool spec_pipe = true;        // SFFGPU_SPEC_PIPE
 };
 
 struct Forest {
   Ctx* ctx;
   sffgpu_forest_cfg cfg;
+  Knobs kn;                         // the environment when the forest was created: never re-read
   DevEngine dev;
   bool device_eligible() const;
   sffk::DevForestView dev_view() const;
@@ -377,17 +371,16 @@ struct Forest {
   bool dev_wave_begin();
   size_t dev_exchange_bytes() const;
   void run_device(int max_waves);
-  bool seq_eligible() const;        // waves of one slot, plain SFF: the persistent single-wavefront loop (k_seq_waves)
+  bool batch_eligible() const;      // waves of one slot the single-wavefront loop can run: may be a member of run_forest_batch
+  bool seq_eligible() const;        // ... and sffgpu_forest_run takes that loop (k_seq_waves / k_spec_waves) for them
   void run_device_seq(int max_waves);
   // one launch of that loop in two halves (run_device_seq, and run_forest_batch below, which launches many forests at once)
   int seq_launch_waves(int waves_left) const;     // waves the next launch may run (waves_left: the caller's bound, 0 = none)
   uint64_t seq_words_end(int batch) const;         // ... and the ring position its engine words have to reach
   sffk::SeqArgs seq_prepare(int batch);            // tops the ring up to there, builds the kernel's arguments
   void seq_lists_fault();                          // SFFK_FAULT_LISTS came back: that wave on the host-replay engine, state back up
-  bool batch_eligible() const;                     // may be a member of run_forest_batch
   bool spec_setup();                // the speculative kernel's scenario tree and buffers; false = k_seq_waves runs the loop
   bool seq_suspended = false;
-  bool test_exchange_self = false;  // SFFGPU_TEST_EXCHANGE_SELF (read when the forest is created): a one-rank forest packs / unpacks its records too
   void sync_host();             // refresh the host mirror (nodes, frontier, borders, counters) from the device
   void fill_stats(sffgpu_forest_stats* out);
   ~Forest();
@@ -477,17 +470,12 @@ struct Forest {
   double knn_r = 0;  // running guess of the k-nearest radius (SFF*)
   std::vector<std::vector<HitRec>> knn_out;   // scratch of the SFF* k-nearest passes
   std::vector<int32_t> edge_ia, edge_ib;      // ... and of its edge batch
-  int hit_cap = 64, nb_cap = 15;  // device list capacities (env SFFGPU_TEST_HITCAP / _NBCAP shrink them in tests)
   // which neighbour-query kernel serves the rounds: k_query_block (flat work lists of a workgroup, 24 hits per sample,
   // neighbourhood lists) where a sample sees few neighbours - steps at least as long as the angular range, or 2-D - and
   // k_query_classify (one wavefront per sample, 64 hits) where the forest fills the angular dimensions too; a list fault
   // switches to the wide kernel for good
   bool query_wide = false;
   void on_list_fault();
-  int star_pass_limit = 0;        // SFF* device stage: most passes of a round's fixed point (0 = the kernels' own limit; SFFGPU_TEST_STAR_PASSES)
-  bool star_tail = true;          // ... the passes after the first as one launch (k_star_tail); SFFGPU_STAR_TAIL=0: one launch per pass
-  int star_tail_wgs = 0;          // ... its grid's upper bound (0 = one workgroup per CU; SFFGPU_STAR_TAIL_WGS)
-  int star_tail_stall = 0;        // ... tests: in every n-th round one workgroup never arrives at the first barrier (SFFGPU_TEST_STAR_STALL=n)
 
   // post-loop path extraction (src/forest.h:420-462, src/problemStruct.h:184-253)
   struct Holder {            // DistanceHolder (src/primitives.h:598-655)
@@ -554,18 +542,13 @@ struct Rrt {
   bool lazy_goal_check(int new_id);                     // src/lazy.h:258-273
   sffgpu_rrt_stats st{};
 
+  Knobs kn;                                             // the environment when the session was created: never re-read
   Rrt(Ctx* c, const sffgpu_rrt_cfg& cf, const double* roots6, int n_roots);
   int add_node(const double* pos, int root_tree, int tree, int parent, double dc, double dr, unsigned it);
   RLink make_link(int a, int b);
   void knn(const double* q, int nq, const int32_t* tree, int k, std::vector<std::vector<int>>& out);
   bool knn_by_grid(const int32_t* tree, int nq, int k) const;
-  bool chain_on = true;   // SFFGPU_RRT_CHAIN (read when the session is created): nearest -> steer -> pose -> parent edge -> k nearest as one chain
-  int split_parts = 2;    // SFFGPU_RRT_SPLIT (1..4): an RRT* wave's member edges in that many batches, the later ones checked while the earlier ones' rows are replayed
-  bool one_chain = true;  // SFFGPU_RRT_ONE_CHAIN: the repaired rows inside the wave's one chain (the device lists them) instead of a second chain
-  bool dry_on = true;     // SFFGPU_RRT_DRY: the replay's nearest-node walk done once ahead, so that only the rows it takes get edges
-  bool repair_on = true;  // SFFGPU_RRT_REPAIR: slots whose nearest node would be an earlier new point of the wave are evaluated from it too
-  int small_mul = 4, small_cap = 48;   // SFFGPU_RRT_SMALL (cap): ... or small_mul x that, up to small_cap slots
-  int grow_pct = 150;     // SFFGPU_RRT_GROW: after a cut wave the next one speculates grow_pct % of what survived (+ 1)
+  static constexpr int small_mul = 4;   // a cut wave is followed by small_mul x what survived, up to kn.rrt_small slots
   void expand(int tree_to_expand, unsigned iteration);
   void draw_target(double rnd[6]);
   int merge_or_link(int tree_to_expand, int new_id, int nb, bool edge_free, int fh, int ns, int& i);

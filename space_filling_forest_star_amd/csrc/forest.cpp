@@ -29,20 +29,19 @@ static double g_star[4] = {0, 0, 0, 0};   // SFF* second stage: k-nearest sweeps
 static double g_wait[3] = {0, 0, 0};   // blocked on: early copy, final sync; [2] = second read pass
 static uint64_t g_items[4] = {0, 0, 0, 0};   // rounds, edge work items, items after the cull, poses after the cull
 static uint64_t g_cnt[4] = {0, 0, 0, 0};   // candidates, skipped by the replay, settled on the device, accepted
-static const bool g_prof = getenv("SFFGPU_PROFILE") != nullptr;
 struct Sec {
   int k;
   Clock::time_point t0;
   explicit Sec(int kk) : k(kk), t0(Clock::now()) {}
   ~Sec() { g_sec[k] += std::chrono::duration<double, std::milli>(Clock::now() - t0).count(); }
 };
-void forest_profile_dump() {
-  if (g_prof && g_items[0]) fprintf(stderr, "[sffgpu per round] edge work items (64-sample chunks) %.0f\n", (double)g_items[1] / g_items[0]);
-  if (g_prof) fprintf(stderr, "[sffgpu candidates] %llu skipped %llu settled %llu\n", (unsigned long long)g_cnt[0], (unsigned long long)g_cnt[1], (unsigned long long)g_cnt[2]);
-  if (g_prof && g_star[3] > 0) fprintf(stderr, "[sffgpu sweep_lists ms] enqueue %.1f wait %.1f unpack %.1f, %.0f queries\n", g_sweep_dbg[0], g_sweep_dbg[1], g_sweep_dbg[2], g_sweep_dbg[3]);
-  if (g_prof && g_star[3] > 0) fprintf(stderr, "[sffgpu SFF* stage 2 ms] k-nearest sweeps %.1f (%.0f passes) member lists %.1f edge batch %.1f\n", g_star[0], g_star[3], g_star[1], g_star[2]);
-  if (g_prof) fprintf(stderr, "[sffgpu waits ms] early copy %.1f final sync %.1f | read pass 2 %.1f\n", g_wait[0], g_wait[1], g_wait[2]);
-  if (g_prof) fprintf(stderr, "[sffgpu host ms] prep %.1f launch %.1f read %.1f records %.1f deser %.1f replay %.1f append %.1f endwave %.1f\n", g_sec[0], g_sec[1], g_sec[2], g_sec[3], g_sec[4], g_sec[5], g_sec[6], g_sec[7]);
+void forest_profile_dump() {   // (SFFGPU_PROFILE: the caller asks its forest's kn.profile)
+  if (g_items[0]) fprintf(stderr, "[sffgpu per round] edge work items (64-sample chunks) %.0f\n", (double)g_items[1] / g_items[0]);
+  fprintf(stderr, "[sffgpu candidates] %llu skipped %llu settled %llu\n", (unsigned long long)g_cnt[0], (unsigned long long)g_cnt[1], (unsigned long long)g_cnt[2]);
+  if (g_star[3] > 0) fprintf(stderr, "[sffgpu sweep_lists ms] enqueue %.1f wait %.1f unpack %.1f, %.0f queries\n", g_sweep_dbg[0], g_sweep_dbg[1], g_sweep_dbg[2], g_sweep_dbg[3]);
+  if (g_star[3] > 0) fprintf(stderr, "[sffgpu SFF* stage 2 ms] k-nearest sweeps %.1f (%.0f passes) member lists %.1f edge batch %.1f\n", g_star[0], g_star[3], g_star[1], g_star[2]);
+  fprintf(stderr, "[sffgpu waits ms] early copy %.1f final sync %.1f | read pass 2 %.1f\n", g_wait[0], g_wait[1], g_wait[2]);
+  fprintf(stderr, "[sffgpu host ms] prep %.1f launch %.1f read %.1f records %.1f deser %.1f replay %.1f append %.1f endwave %.1f\n", g_sec[0], g_sec[1], g_sec[2], g_sec[3], g_sec[4], g_sec[5], g_sec[6], g_sec[7]);
 }
 static double ms_since(Clock::time_point t0) {
   return std::chrono::duration<double, std::milli>(Clock::now() - t0).count();
@@ -96,6 +95,7 @@ bool Forest::all_frontiers_empty() const {
 }
 
 Forest::Forest(Ctx* c, const sffgpu_forest_cfg& cf, const double* roots6, int n_roots) : ctx(c), cfg(cf) {
+  kn = c->kn = Knobs::from_env();
   if (cfg.wave < 1) cfg.wave = 1;
   if (cfg.dim != 2 && cfg.dim != 6) throw HipError{"forest: dim must be 2 or 6"};
   if (cfg.world < 1) cfg.world = 1;
@@ -113,11 +113,9 @@ Forest::Forest(Ctx* c, const sffgpu_forest_cfg& cf, const double* roots6, int n_
   }
   {   // which engine commits the rounds: the device-resident one (forest_dev.cpp) for plain SFF and SFF*,
       // the host replay below for goal / priority modes (and when SFFGPU_ENGINE=host asks for it)
-    const char* e = getenv("SFFGPU_ENGINE");
-    const std::string want = e ? e : "";
     // (every wave size: at wave = 1 - the reference's own order - the device engine's one graph launch + one status
     // read per wave is 1.3x the host replay's per-round synchronisation, at wave 64 1.6x: profiles/r3_small_waves.txt)
-    dev.on = device_eligible() && want != "host" && cfg.wave <= 64 * SFFK_DEV_MAX_GROUPS;
+    dev.on = device_eligible() && kn.engine != Knobs::ENGINE_HOST && cfg.wave <= 64 * SFFK_DEV_MAX_GROUPS;
   }
   // (device engine: a wave of new nodes past the budget plus the round's temporaries behind them)
   ctx->store_reset(std::max(cfg.node_budget, 4096) + (dev.on ? 2 * cfg.wave + 128 : cfg.wave + 64));
@@ -134,8 +132,7 @@ Forest::Forest(Ctx* c, const sffgpu_forest_cfg& cf, const double* roots6, int n_
     double cell = 1.01 * std::max(cfg.sampling_dist, cfg.dist_tree) + 4 * ctx->sweep_eps();
     ctx->grid_rebuilds = 0;
     ctx->grid_exhausted = false;
-    ctx->grid_bk = 8;
-    if (const char* e = getenv("SFFGPU_TEST_GRID_BK")) ctx->grid_bk = std::max(1, std::min(8, atoi(e)));   // tests: tiny buckets to start with
+    ctx->grid_bk = kn.test_grid_bk;
     ctx->grid_cell0 = cell;
     query_wide = cfg.dim != 2 && std::min(cfg.sampling_dist, cfg.dist_tree) < 2.0 * 3.14159265358979323846;
     if (use_priority()) query_wide = true; // (the heaps crowd the samples around the trees' best nodes: more than 24 hits happen)
@@ -175,32 +172,14 @@ Forest::Forest(Ctx* c, const sffgpu_forest_cfg& cf, const double* roots6, int n_
   }
   memset(&st, 0, sizeof st);
   knn_r = 2.5 * cfg.sampling_dist;
-  if (const char* e = getenv("SFFGPU_TEST_HITCAP")) hit_cap = std::min(64, std::max(1, atoi(e)));  // one lane per hit
-  dev.ord_enabled = !(getenv("SFFGPU_NO_ORDER") && atoi(getenv("SFFGPU_NO_ORDER")) != 0);   // spatial order of a wave's slots (sffk::OrderView)
-  if (const char* e = getenv("SFFGPU_ORDER_MIN_WAVE")) dev.ord_min_wave = std::max(2, atoi(e));
-  if (hit_cap < 24) query_wide = true;   // (tests shrink the hit list of the wide kernel)
-  if (const char* e = getenv("SFFGPU_TEST_NBCAP")) nb_cap = std::max(1, atoi(e));
-  if (const char* e = getenv("SFFGPU_TEST_STAR_PASSES")) star_pass_limit = std::max(1, atoi(e));
-  if (getenv("SFFGPU_TEST_EXCHANGE_SELF")) test_exchange_self = true;
-  if (const char* e = getenv("SFFGPU_STAR_TAIL")) star_tail = atoi(e) != 0;
-  // waves of one slot: the speculative kernel's shape (k_spec_waves; forest_dev.cpp: spec_setup)
-  if (const char* e = getenv("SFFGPU_SPEC")) dev.spec_off = atoi(e) == 0;
-  if (const char* e = getenv("SFFGPU_SPEC_DEPTH")) dev.spec_depth = atoi(e);
-  if (const char* e = getenv("SFFGPU_SPEC_SETS")) dev.spec_sets_want = atoi(e);
-  if (const char* e = getenv("SFFGPU_TEST_SPEC_STALL")) dev.spec_test_stall = atoi(e);
-  if (const char* e = getenv("SFFGPU_SPEC_PIPE")) dev.spec_pipe = atoi(e) != 0;
-  if (const char* e = getenv("SFFGPU_NO_DEV_TRIG")) dev.dev_trig_off = atoi(e) != 0;
-  if (const char* e = getenv("SFFGPU_STAR_TAIL_WGS")) star_tail_wgs = std::max(1, atoi(e));
-  if (const char* e = getenv("SFFGPU_TEST_STAR_STALL")) star_tail_stall = std::max(0, atoi(e));
-  if (const char* e = getenv("SFFGPU_NO_GRAPH")) dev.graph_enabled = atoi(e) == 0;
-  else if (cfg.optimize) {
+  if (kn.test_hitcap < 24) query_wide = true;   // (tests shrink the hit list of the wide kernel)
+  dev.spec_off = !kn.spec;   // waves of one slot: the speculative kernel (k_spec_waves; forest_dev.cpp: spec_setup)
+  if (kn.no_graph >= 0) dev.graph_enabled = kn.no_graph == 0;
+  else if (cfg.optimize && kn.profiler_preloaded) {
     // rocprofv3 (ROCm 7.2) crashes while tracing replays of the SFF* wave graph (~130 kernel nodes; the plain SFF graph
     // of ~35 nodes traces fine): under the profiler SFF* waves are launched kernel by kernel
-    const char* pre = getenv("LD_PRELOAD");
-    if (pre && strstr(pre, "rocprofiler")) {
-      dev.graph_enabled = false;
-      fprintf(stderr, "[sffgpu] profiler library in LD_PRELOAD: SFF* waves are launched kernel by kernel (SFFGPU_NO_GRAPH=0 / 1 overrides)\n");
-    }
+    dev.graph_enabled = false;
+    fprintf(stderr, "[sffgpu] profiler library in LD_PRELOAD: SFF* waves are launched kernel by kernel (SFFGPU_NO_GRAPH=0 / 1 overrides)\n");
   }
 }
 
@@ -284,6 +263,7 @@ void Forest::fill_stats(sffgpu_forest_stats* out) {
     s.poses_executed = k.poses_executed;
     s.segments_executed = k.segments_executed;
     s.samples_executed = k.samples_executed;
+    if (use_priority() && kn.prio_seq) s.prio_seq_waves += k.waves - st.waves;   // (as sync_host will count them)
     s.waves = k.waves;
     s.sweeps = k.rounds;
     s.sweep_nodes = k.round_nodes;
@@ -518,7 +498,7 @@ void Forest::round_begin() {
   //   k_sample_steer -> k_store_write (temporaries) -> k_sweep -> k_classify -> k_collide_poses
   //   -> k_collide_segments_dyn -> D2H {samples, flags, neighbour records, pose / edge answers}
   const int words_per = cfg.dim == 2 ? 1 : 6;
-  const int CAP = hit_cap, NBCAP = nb_cap, STRIDE = 1 + NBCAP;
+  const int CAP = kn.test_hitcap, NBCAP = kn.test_nbcap, STRIDE = 1 + NBCAP;
   // packed host input: words (n*6 u64) | parent (n i32) | force (n u8)
   const size_t in_words = 0, in_parent = (size_t)n * 48, in_force = in_parent + (size_t)n * 4;
   const size_t in_preset = ((in_force + (size_t)n + 15) / 16) * 16;   // (libm parity mode: n x 6 sample positions)
@@ -542,7 +522,7 @@ void Forest::round_begin() {
         sample_point_libm(hw + 6 * (size_t)i, nodes[cands[i].expanded].pos, cfg.sampling_dist, cfg.dim, hs + 6 * (size_t)i);
     }
   }
-  c.timing_on = c.timer_stride <= 1 || st.sweeps % (uint64_t)c.timer_stride == 0;
+  c.timing_on = kn.timer_stride <= 1 || st.sweeps % (uint64_t)kn.timer_stride == 0;
   c.round_scope = true;
   const uint64_t* d_words = reinterpret_cast<const uint64_t*>(c.r_in.as<char>() + in_words);
   const int32_t* d_parent = reinterpret_cast<const int32_t*>(c.r_in.as<char>() + in_parent);
@@ -641,7 +621,7 @@ void Forest::round_begin() {
   ca.items_cap = list_cap;
   ca.sub = c.r_sub.as<int32_t>();
   ca.pose_hit = d_pose;
-  const bool blocked = sffk::launch_query_classify(c.stream, c.gridv, &c.tgridv, c.store_view(), c.r_q.as<sffk::SweepQuery>(), ca, &c.envv);
+  const bool blocked = sffk::launch_query_classify(c.stream, kn, c.gridv, &c.tgridv, c.store_view(), c.r_q.as<sffk::SweepQuery>(), ca, &c.envv);
   c.time_end();
   c.time_begin(T_COLLIDE);
   c.p_out.ensure(o_bytes);
@@ -656,7 +636,7 @@ void Forest::round_begin() {
   sffk::TempGridRef tref_keep = tref;
   tref_keep.tg = sffk::GridView{};
   tref_keep.n = 0;
-  sffk::launch_collide_items(c.stream, c.envv, c.robv, d_pos, n, ca.rec_flags, d_pose, ca.seg_a, ca.seg_b, ca.seg_ns,
+  sffk::launch_collide_items(c.stream, kn, c.envv, c.robv, d_pos, n, ca.rec_flags, d_pose, ca.seg_a, ca.seg_b, ca.seg_ns,
                              STRIDE, ca.ctrl, c.r_items.p, ca.items_cap, ca.sub, ca.first_hit, ca.seg_ovf, cfg.optimize ? &tref_keep : &tref,
                              nullptr, blocked ? &ca : nullptr);
   c.time_end();
@@ -1223,7 +1203,7 @@ void Forest::round_commit(const int32_t* all, int total_words, const int32_t* co
   }
   g_sec[4] += ms_since(_t4);
   auto _t5 = Clock::now();
-  if (getenv("SFFGPU_DIGEST")) {
+  if (kn.digest) {
     for (int i = 0; i < n; ++i) {
       const Cand& cd = cands[i];
       if (!cd.in_lim) continue;

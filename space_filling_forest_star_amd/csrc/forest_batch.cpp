@@ -32,10 +32,6 @@ namespace sff {
 using Clock = std::chrono::steady_clock;
 static double ms_since(Clock::time_point t0) { return std::chrono::duration<double, std::milli>(Clock::now() - t0).count(); }
 
-bool Forest::batch_eligible() const {   // seq_eligible() without its knob: what the single-wavefront loop can run
-  return dev.on && cfg.wave == 1 && cfg.world == 1 && num_roots <= 64 && !cfg.has_goal && !use_priority();
-}
-
 namespace {
 struct ArgBufs {   // the members' SeqArgs: pinned staging + device array, SFF members first
   PinBuf h;

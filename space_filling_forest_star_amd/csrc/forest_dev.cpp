@@ -41,8 +41,7 @@ bool Forest::device_eligible() const {
   // (measured on dense_3D, 100 k nodes: 73 k nodes/s at waves of 64 slots against the host engine's 29 k, 0.83 M at 1 024
   // against 98 k, 1.6 M at 8 192; waves of one slot - the reference's own loop - stay on the host engine;
   // SFFGPU_PRIO_DEVICE=0 keeps the whole mode there)
-  const char* const knob = getenv("SFFGPU_PRIO_DEVICE");
-  const int min_wave = (knob && !atoi(knob)) ? 0x7fffffff : 2;
+  const int min_wave = kn.prio_device ? 2 : 0x7fffffff;
   if (cfg.has_goal || cfg.wave < min_wave || cfg.world > 1) return false;
   const long long heaps_n = (long long)num_roots * (num_roots - 1);
   const long long cap = (long long)std::max(cfg.node_budget, 4096) + 2LL * cfg.wave + 128;
@@ -227,10 +226,10 @@ void Forest::dev_star_setup() {
     d.s_backup.ensure(sizeof(sffk::DevCtrl));
     // (survivor items of ONE pass: the chunks of the reachable member edges the clearance bits leave open)
     d.s_items_cap = (int)std::min<size_t>(16 * W + 65536, (size_t)1 << 26) / SFFK_SUBLISTS * SFFK_SUBLISTS;
-    if (const char* e = getenv("SFFGPU_TEST_STAR_ITEMS")) d.s_items_cap = std::max(SFFK_SUBLISTS, atoi(e)) / SFFK_SUBLISTS * SFFK_SUBLISTS;
+    if (kn.test_star_items >= 0) d.s_items_cap = std::max(SFFK_SUBLISTS, kn.test_star_items) / SFFK_SUBLISTS * SFFK_SUBLISTS;
     d.s_items.ensure((size_t)d.s_items_cap * sizeof(sffk::SurvivorItem));
     HIPCHK(hipMemset(d.s_sub.p, 0, d.s_sub.cap));
-    if (getenv("SFFGPU_PROFILE")) {
+    if (kn.profile) {
       d.s_dbg.ensure(32 * 8);
       HIPCHK(hipMemset(d.s_dbg.p, 0, 32 * 8));
     }
@@ -285,7 +284,7 @@ sffk::DevForestView Forest::dev_view() const {
     // come from k_prio_begin - and only with the node grid in place; SFFGPU_NO_ORDER=1 switches it off
     const sffk::GridView& g = ctx->gridv;
     // (waves below 4 096 slots: a few hundred samples per round share one XCD's L2 anyway, the bookkeeping only costs)
-    if (d.ord_enabled && !use_priority() && d.ord_hist.p && g.cnt && g.nx > 0 && cfg.wave >= d.ord_min_wave) {
+    if (!kn.no_order && !use_priority() && d.ord_hist.p && g.cnt && g.nx > 0 && cfg.wave >= kn.order_min_wave) {
       sffk::OrderView& o = v.ord;
       o.hist = d.ord_hist.as<int32_t>(); o.start = d.ord_start.as<int32_t>();
       o.slot_key = d.ord_key.as<int32_t>(); o.slot_rank = d.ord_rank.as<int32_t>();
@@ -310,16 +309,14 @@ sffk::DevForestView Forest::dev_view() const {
     v.prio.slot_tree = d.slot_tree.as<int32_t>(); v.prio.slot_heap = d.slot_heap.as<int32_t>(); v.prio.slot_idx = d.slot_idx.as<int32_t>();
     v.prio.counters = d.hp_cnt.as<int32_t>(); v.prio.gen = d.hp_gen.as<int32_t>();
     v.prio.slot_word = d.slot_word.as<unsigned long long>();
-    static const bool seq_only = getenv("SFFGPU_PRIO_SEQ") && atoi(getenv("SFFGPU_PRIO_SEQ")) != 0;   // (tests: the sequential picks)
-    v.prio.plan = seq_only ? nullptr : d.hp_plan.as<int32_t>();
+    v.prio.plan = kn.prio_seq ? nullptr : d.hp_plan.as<int32_t>();   // (null: the sequential picks of k_prio_begin; st.prio_seq_waves counts them)
     v.prio.bias = cfg.priority_bias;
   }
-  static const int profile = getenv("SFFGPU_PROFILE") ? 1 : 0;
-  v.profile = profile;
+  v.profile = kn.profile ? 1 : 0;
   v.qclk_sh = d.qclk_sh.as<unsigned long long>();
-  v.host_status = (d.zc_status && d.h_ctrl.p) ? d.h_ctrl.as<sffk::DevCtrl>() : nullptr;   // (hipHostMalloc: one address on both sides)
+  v.host_status = (!kn.no_zc_status && d.h_ctrl.p) ? d.h_ctrl.as<sffk::DevCtrl>() : nullptr;   // (hipHostMalloc: one address on both sides)
   v.kc_trace = d.kc_trace.as<unsigned long long>();
-  v.kc_trace_round = getenv("SFFGPU_KC_TRACE") ? atoi(getenv("SFFGPU_KC_TRACE")) : -1;
+  v.kc_trace_round = kn.kc_trace;
   v.b_n1 = d.b_n1.as<int32_t>();
   v.b_n2 = d.b_n2.as<int32_t>();
   v.b_ta = d.b_ta.as<int32_t>();
@@ -392,7 +389,7 @@ void Forest::dev_size_border_arrays(int want_cap) {
     d.b_tb.ensure((size_t)want_cap * 4);
     d.b_dist.ensure((size_t)want_cap * 8);
   }
-  const uint64_t want_tab = next_pow2((uint64_t)std::max(getenv("SFFGPU_TEST_BORDER_CAP") ? 64 : 1 << 16, 4 * d.border_cap));
+  const uint64_t want_tab = next_pow2((uint64_t)std::max(kn.test_border_cap >= 0 ? 64 : 1 << 16, 4 * d.border_cap));
   if (want_tab > d.bt_size) {
     d.bt_size = want_tab;
     d.bt_key.release();
@@ -484,14 +481,13 @@ void Forest::dev_upload_state() {
     if (cfg.libm_sampling) {
       d.trig.ensure((size_t)d.ring_words * 24);
       d.h_trig.ensure((size_t)d.ring_words * 24);
-    } else if (cfg.wave == 1 && !d.dev_trig_off) {
+    } else if (cfg.wave == 1 && !kn.no_dev_trig) {
       // waves of one slot: the one wavefront that is waited for looks its sample's cos / sin / acos up (k_ring_trig fills the table)
       d.trig.ensure((size_t)d.ring_words * 24);
       d.dev_trig = true;
     }
     d.ctrl.ensure(sizeof(sffk::DevCtrl));
     d.h_ctrl.ensure((size_t)SFFK_STATUS_RING * sizeof(sffk::DevCtrl));   // (>= 2: the copy path's two slots)
-    d.zc_status = !(getenv("SFFGPU_NO_ZC_STATUS") && atoi(getenv("SFFGPU_NO_ZC_STATUS")) != 0);
     d.slot_node.ensure((size_t)wave * 4);
     d.slot_pos.ensure((size_t)wave * 4);
     d.act_slot.ensure((size_t)wave * 4);
@@ -520,7 +516,7 @@ void Forest::dev_upload_state() {
       HIPCHK(hipMemsetAsync(d.ord_cnt.p, 0, 2 * n_sub * SFFK_ORD_CNT_STRIDE * 4, c.stream));
     }
     HIPCHK(hipMemsetAsync(d.ord_hist.p, 0, (size_t)SFFK_ORD_BUCKETS * 4, c.stream));
-    if (getenv("SFFGPU_KC_TRACE")) {
+    if (kn.kc_trace >= 0) {
       d.kc_trace.ensure(((size_t)wave / 64 + 2) * 64);
       HIPCHK(hipMemsetAsync(d.kc_trace.p, 0, ((size_t)wave / 64 + 2) * 64, c.stream));
     }
@@ -545,7 +541,7 @@ void Forest::dev_upload_state() {
     // (borders end up at 6-7 % of the nodes on the maps of BASELINE.json: room for a tenth of the node budget, so that a
     // job sized by its budget does not stop in the middle to grow these arrays - 4 ms at 850 k nodes on the bench job)
     int first_cap = std::max(std::max(1 << 16, 2 * (nb + wave)), cfg.node_budget > 0 ? cfg.node_budget / 10 + 2 * wave : 0);
-    if (const char* e = getenv("SFFGPU_TEST_BORDER_CAP")) first_cap = std::max(nb + 1, atoi(e));   // tests: force growth
+    if (kn.test_border_cap >= 0) first_cap = std::max(nb + 1, kn.test_border_cap);   // tests: force growth
     dev_size_border_arrays(first_cap);
   }
   if (cfg.optimize) dev_star_setup();
@@ -762,6 +758,7 @@ void Forest::sync_host() {
   st.poses_executed = k.poses_executed;
   st.segments_executed = k.segments_executed;
   st.samples_executed = k.samples_executed;
+  if (use_priority() && kn.prio_seq) st.prio_seq_waves += k.waves - st.waves;   // (device waves: PrioView::plan was null, dev_view)
   st.waves = k.waves;
   st.sweeps = k.rounds;
   st.sweep_nodes = k.round_nodes;
@@ -837,7 +834,7 @@ static DevRoundBufs dev_round_bufs(Forest& F) {
   Ctx& c = *F.ctx;
   DevRoundBufs B{};
   const int n = F.cfg.wave;   // launch bound; the kernels read the real count from DevCtrl
-  B.n = n; B.CAP = F.hit_cap; B.NBCAP = F.nb_cap; B.STRIDE = 1 + B.NBCAP;
+  B.n = n; B.CAP = F.kn.test_hitcap; B.NBCAP = F.kn.test_nbcap; B.STRIDE = 1 + B.NBCAP;
   const size_t rec_ints = (size_t)n * (2 + 2 * B.NBCAP);
   const size_t o_pos = 0, o_pd = o_pos + (size_t)n * 48, o_lim = o_pd + (size_t)n * 8,
                o_rec = o_lim + ((size_t)n + 15) / 16 * 16, o_ns = o_rec + rec_ints * 4,
@@ -906,7 +903,7 @@ static sffk::ResolveArgs dev_resolve_args(Forest& F, const DevRoundBufs& B) {
 
 size_t Forest::dev_exchange_bytes() const {   // what one rank contributes to the all-gather of a round
   const int per_rank = (cfg.wave + cfg.world - 1) / cfg.world;
-  return (size_t)per_rank * sffk::record_words(nb_cap) * 4;
+  return (size_t)per_rank * sffk::record_words(kn.test_nbcap) * 4;
 }
 
 void Forest::dev_enqueue_begin() {
@@ -979,7 +976,7 @@ void Forest::dev_enqueue_round_eval(void* send_dev, bool sample) {
   const int n = B.n;
   const int32_t* dev_n = reinterpret_cast<const int32_t*>(d.ctrl.p);   // {n_act, halt}
   c.timing_on = d.force_timing >= 0 ? d.force_timing != 0
-                                   : (c.timer_stride <= 1 || d.rounds_enqueued % (uint64_t)c.timer_stride == 0);
+                                   : (kn.timer_stride <= 1 || d.rounds_enqueued % (uint64_t)kn.timer_stride == 0);
   d.round_timing = c.timing_on;   // (the commit of this round is timed like its evaluation)
   c.round_scope = true;
   ++d.rounds_enqueued;
@@ -1033,7 +1030,7 @@ void Forest::dev_enqueue_round_eval(void* send_dev, bool sample) {
   ca.items_cap = B.list_cap;
   ca.sub = c.r_sub.as<int32_t>();
   ca.pose_hit = B.d_pose;
-  const bool blocked = sffk::launch_query_classify(c.stream, c.gridv, &c.tgridv, c.store_view(), c.r_q.as<sffk::SweepQuery>(), ca, &c.envv);
+  const bool blocked = sffk::launch_query_classify(c.stream, kn, c.gridv, &c.tgridv, c.store_view(), c.r_q.as<sffk::SweepQuery>(), ca, &c.envv);
   c.time_end();
   c.time_begin(T_COLLIDE);
   sffk::TempGridRef tref{c.tgridv, c.sx.as<float>() + d.temp_base, c.sy.as<float>() + d.temp_base,
@@ -1042,7 +1039,7 @@ void Forest::dev_enqueue_round_eval(void* send_dev, bool sample) {
   sffk::TempGridRef tref_keep = tref;
   tref_keep.tg = sffk::GridView{};
   tref_keep.n = 0;
-  sffk::launch_collide_items(c.stream, c.envv, c.robv, B.d_pos, n, ca.rec_flags, B.d_pose, ca.seg_a, ca.seg_b, ca.seg_ns,
+  sffk::launch_collide_items(c.stream, kn, c.envv, c.robv, B.d_pos, n, ca.rec_flags, B.d_pose, ca.seg_a, ca.seg_b, ca.seg_ns,
                              B.STRIDE, ca.ctrl, c.r_items.p, ca.items_cap, ca.sub, ca.first_hit, ca.seg_ovf,
                              cfg.optimize ? &tref_keep : &tref, dev_n, blocked ? &ca : nullptr);
   c.time_end();
@@ -1091,10 +1088,12 @@ void Forest::dev_enqueue_round_commit(const void* recv_dev, bool sample_next) {
     sl.cell_edge = c.grid_cell;
     sl.slack = 8 * c.sweep_eps();
     sl.cube_reach = 2.0 * cfg.sampling_dist;
-    sl.passes = star_pass_limit;
-    sl.tail = star_tail ? 1 : 0;
-    sl.tail_wgs = star_tail_wgs;
-    sl.tail_stall = star_tail_stall;
+    sl.passes = kn.test_star_passes;
+    sl.tail = kn.star_tail ? 1 : 0;
+    sl.tail_wgs = kn.star_tail_wgs;
+    sl.tail_stall = kn.test_star_stall;
+    sl.knn_lone = kn.star_knn == Knobs::STAR_KNN_LONE;
+    sl.seg_blocks = kn.seg_blocks;
     sffk::launch_commit(c.stream, ra, B.n, &sl, sample_next ? &next : nullptr);
   } else {
     sffk::launch_commit(c.stream, ra, B.n, nullptr, sample_next ? &next : nullptr);
@@ -1110,8 +1109,8 @@ void Forest::dev_enqueue_end(int slot) {
   if (use_priority()) sffk::launch_prio_end(c.stream, dev_view(), c.store_view());
   sffk::launch_wave_end(c.stream, dev_view(), c.gridv.ovf_cnt, c.tgridv.ovf_cnt,
                         cfg.optimize ? d.s_acc.as<unsigned long long>() : nullptr);
-  d.status_copied[slot] = !d.zc_status;
-  if (d.zc_status) d.status_of[slot] = d.status_next++;   // (k_wave_end_wide published the block itself)
+  d.status_copied[slot] = kn.no_zc_status;
+  if (!kn.no_zc_status) d.status_of[slot] = d.status_next++;   // (k_wave_end_wide published the block itself)
   else HIPCHK(hipMemcpyAsync(d.h_ctrl.as<sffk::DevCtrl>() + slot, d.ctrl.p, sizeof(sffk::DevCtrl), hipMemcpyDeviceToHost, c.stream));
   HIPCHK(hipEventRecord(slot ? d.ev_wave2 : d.ev_wave, c.stream));
 }
@@ -1141,7 +1140,7 @@ uint64_t Forest::dev_launch_signature() {
   mix(ptrs, sizeof ptrs);
   const double scal[] = {c.sweep_eps(), c.grid_cell, cfg.sampling_dist, cfg.dist_tree};
   mix(scal, sizeof scal);
-  const int ints[] = {cfg.threshold_misses, star_pass_limit, cfg.wave, c.store_cap, dev.temp_base, hit_cap, nb_cap, query_wide ? 1 : 0};
+  const int ints[] = {cfg.threshold_misses, kn.test_star_passes, cfg.wave, c.store_cap, dev.temp_base, kn.test_hitcap, kn.test_nbcap, query_wide ? 1 : 0};
   mix(ints, sizeof ints);
   return x ? x : 1;
 }
@@ -1151,7 +1150,7 @@ void Forest::dev_enqueue_wave_kernels(bool sharded, size_t words) {
   // round r's append and round r + 1's sampling are one launch (k_append_sample): the rounds alternate between two sets
   // of sample arrays, only the first round of the wave samples on its own
   const int R = std::max(1, cfg.threshold_misses);
-  static const bool fuse = !(getenv("SFFGPU_NO_FUSED_SAMPLE") && atoi(getenv("SFFGPU_NO_FUSED_SAMPLE")) != 0);
+  const bool fuse = !kn.no_fused_sample;
   for (int r = 0; r < R; ++r) {
     dev.round_parity = fuse ? (r & 1) : 0;
     dev_enqueue_round_eval(sharded ? x_send.p : nullptr, !fuse || r == 0);
@@ -1173,7 +1172,7 @@ void Forest::dev_enqueue_wave(int slot) {
     d.ring_pending = false;
   }
   // (SFFGPU_TEST_EXCHANGE_SELF: a one-rank forest packs, all-gathers and unpacks too - the collective on one GPU)
-  const bool self_exchange = test_exchange_self;
+  const bool self_exchange = kn.test_exchange_self;
   const bool sharded = cfg.world > 1 || (self_exchange && (ctx->rccl_comm != nullptr || ctx->xchg_fn != nullptr));
   size_t words = 0;
   if (sharded) {   // this rank's answer records of a round -> all ranks' (ncclAllGather between device buffers)
@@ -1181,9 +1180,9 @@ void Forest::dev_enqueue_wave(int slot) {
     x_send.ensure(words * 4);
     x_recv.ensure(words * 4 * (size_t)cfg.world);
   }
-  // every timer_stride-th wave is launched kernel by kernel with HIP events around the timed kernels (the figures are
+  // every kn.timer_stride-th wave is launched kernel by kernel with HIP events around the timed kernels (the figures are
   // scaled to all waves); the others replay the captured graph
-  const bool timed_wave = c.timer_stride <= 1 || d.waves_enqueued % (uint64_t)c.timer_stride == 0;
+  const bool timed_wave = kn.timer_stride <= 1 || d.waves_enqueued % (uint64_t)kn.timer_stride == 0;
   ++d.waves_enqueued;
   const bool use_graph = d.graph_enabled && !sharded && !timed_wave;
   if (use_graph) {
@@ -1225,8 +1224,8 @@ void Forest::dev_enqueue_wave(int slot) {
     dev_enqueue_wave_kernels(sharded, words);
     d.force_timing = -1;
   }
-  d.status_copied[slot] = !d.zc_status;
-  if (d.zc_status) d.status_of[slot] = d.status_next++;   // (k_wave_end_wide published the block itself)
+  d.status_copied[slot] = kn.no_zc_status;
+  if (!kn.no_zc_status) d.status_of[slot] = d.status_next++;   // (k_wave_end_wide published the block itself)
   else HIPCHK(hipMemcpyAsync(d.h_ctrl.as<sffk::DevCtrl>() + slot, d.ctrl.p, sizeof(sffk::DevCtrl), hipMemcpyDeviceToHost, c.stream));
   HIPCHK(hipEventRecord(slot ? d.ev_wave2 : d.ev_wave, c.stream));
   dev.host_stale = true;
@@ -1256,7 +1255,7 @@ int Forest::dev_finish_wave(double* wait_ms, int slot, bool stream_idle) {
   if (!stream_idle) return d.last.fault;
   d.host_stale = true;
   const sffk::DevCtrl& s = d.last;
-  static const bool prof = getenv("SFFGPU_PROFILE") != nullptr;
+  const bool prof = kn.profile;
   const auto t_ev = Clock::now();
   if (s.fault) {
     const int fault = s.fault;
@@ -1329,16 +1328,18 @@ bool Forest::dev_wave_begin() {
   return true;
 }
 
-bool Forest::seq_eligible() const {
-  static const bool off = getenv("SFFGPU_NO_SEQ") != nullptr && atoi(getenv("SFFGPU_NO_SEQ")) != 0;
-  return dev.on && cfg.wave == 1 && cfg.world == 1 && !off && !seq_suspended && num_roots <= 64 && !cfg.has_goal && !use_priority();
+// waves of one slot the persistent single-wavefront loop can run (a member of run_forest_batch needs no more) ...
+bool Forest::batch_eligible() const {
+  return dev.on && cfg.wave == 1 && cfg.world == 1 && num_roots <= 64 && !cfg.has_goal && !use_priority();
 }
+// ... and sffgpu_forest_run takes that loop for them
+bool Forest::seq_eligible() const { return batch_eligible() && !kn.no_seq && !seq_suspended; }
 
 // The scenario tree of k_spec_waves (kernels.h: SpecArgs).  Plain SFF: the full tree of outcomes (accept at attempt
 // 0 .. TM-1 | all fail) to SFFGPU_SPEC_DEPTH waves (default 3: 1 + 6 + 36 scenarios at ThresholdMisses = 5, one workgroup
 // per scenario and attempt), cut where the grid would no longer be resident at once; SFF*: the chain of all-fail
 // scenarios.  SFFGPU_SPEC_SETS sets of workers take the steps in turn (default 1).  SFFGPU_SPEC=0 keeps the single
-// wavefront (k_seq_waves).  All read when the forest is created (forest.cpp).
+// wavefront (k_seq_waves).  All in the forest's snapshot (Forest::kn).
 static const size_t SPEC_HEAD = 4096;   // bytes in front of the records: 4 x 64 control-block granules, the step word
 bool Forest::spec_setup() {
   DevEngine& d = dev;
@@ -1346,8 +1347,8 @@ bool Forest::spec_setup() {
   const int TM = std::max(1, cfg.threshold_misses);
   if (d.spec_n_sc > 0 && d.spec_tm == TM) return true;
   if (TM > 8) { d.spec_off = true; return false; }
-  const int depth = std::max(1, std::min(d.spec_depth > 0 ? d.spec_depth : (cfg.optimize ? 4 : 3), SFFK_SPEC_DEPTH));
-  const int sets = std::max(1, std::min(d.spec_sets_want, 4));
+  const int depth = std::max(1, std::min(kn.spec_depth > 0 ? kn.spec_depth : (cfg.optimize ? 4 : 3), SFFK_SPEC_DEPTH));
+  const int sets = std::max(1, std::min(kn.spec_sets, 4));
   struct Sc { int level; int out[SFFK_SPEC_DEPTH]; int anc[SFFK_SPEC_DEPTH]; int child[9]; };
   std::vector<Sc> tab;
   Sc root{};
@@ -1422,7 +1423,7 @@ sffk::SeqArgs Forest::seq_prepare(int batch) {
   a.grid_ovf_src = c.gridv.ovf_cnt;
   a.dim = cfg.dim;
   a.max_waves = batch;
-  a.hit_cap = hit_cap;
+  a.hit_cap = kn.test_hitcap;
   a.grid_ovf_limit = c.grid_rebuild_at();
   a.optimize = cfg.optimize ? 1 : 0;
   if (cfg.optimize) {
@@ -1480,7 +1481,7 @@ void Forest::run_device_seq(int max_waves) {
       HIPCHK(hipStreamWaitEvent(c.stream, d.ev_ring, 0));
       d.ring_pending = false;
     }
-    const char* trace_path = getenv("SFFGPU_SEQ_TRACE");
+    const char* trace_path = kn.seq_trace.empty() ? nullptr : kn.seq_trace.c_str();
     DevBuf trace_buf;
     if (trace_path) {
       trace_buf.ensure((size_t)batch * 32);
@@ -1502,10 +1503,10 @@ void Forest::run_device_seq(int max_waves) {
       sa.cur_step = reinterpret_cast<int32_t*>(d.spec_area.as<uint8_t>() + SPEC_HEAD - 256);
       sa.rec = reinterpret_cast<unsigned long long*>(d.spec_area.as<uint8_t>() + SPEC_HEAD);
       sa.timeout_ticks = 20000000ULL;   // 200 ms
-      sa.pipeline = d.spec_pipe ? 1 : 0;
-      if (d.spec_test_stall && st.spec_steps == 0 && d.last.spec_steps == 0) sa.test_stall = d.spec_test_stall;
+      sa.pipeline = kn.spec_pipe ? 1 : 0;
+      if (kn.test_spec_stall && st.spec_steps == 0 && d.last.spec_steps == 0) sa.test_stall = kn.test_spec_stall;
       const size_t rec_bytes = (size_t)sa.n_sets * sa.n_slots * SFFK_SPEC_REC * 8;
-      if (getenv("SFFGPU_PROFILE")) sa.hb = reinterpret_cast<unsigned long long*>(d.spec_area.as<uint8_t>() + SPEC_HEAD + rec_bytes);
+      if (kn.profile) sa.hb = reinterpret_cast<unsigned long long*>(d.spec_area.as<uint8_t>() + SPEC_HEAD + rec_bytes);
       HIPCHK(hipMemsetAsync(d.spec_area.p, 0, d.spec_area.cap, c.stream));
       sffk::launch_spec_waves(c.stream, sa);
     } else {
@@ -1523,7 +1524,7 @@ void Forest::run_device_seq(int max_waves) {
       if (FILE* fp = fopen(trace_path, "ab")) { fwrite(tr.data(), 4, tr.size(), fp); fclose(fp); }
       trace_buf.release();
     }
-    if (spec && getenv("SFFGPU_PROFILE")) {
+    if (spec && kn.profile) {
       const int nw = d.spec_sets * d.spec_n_sc * d.spec_tm;
       unsigned long long wq[22];
       HIPCHK(hipMemcpy(wq, d.spec_area.as<uint8_t>() + SPEC_HEAD + (size_t)nw * SFFK_SPEC_REC * 8 + ((size_t)nw + 64) * 8, sizeof wq, hipMemcpyDeviceToHost));
@@ -1537,7 +1538,7 @@ void Forest::run_device_seq(int max_waves) {
     }
     if (spec && d.last.spec_stalled) {   // (its workgroups were not resident together: the single wavefront from here on)
       d.spec_off = true;
-      if (getenv("SFFGPU_PROFILE")) {
+      if (kn.profile) {
         fprintf(stderr, "[sffgpu k_spec_waves] a record did not arrive: back to k_seq_waves\n");
         const int nw = d.spec_sets * d.spec_n_sc * d.spec_tm;
         std::vector<unsigned long long> hb((size_t)nw + 8 + 34);
@@ -1553,7 +1554,7 @@ void Forest::run_device_seq(int max_waves) {
   }
   st.total_ms += ms_since(t0);
   st.host_ms += ms_since(t0) - wait_ms;
-  if (getenv("SFFGPU_PROFILE") && d.last.spec_steps > 0) {
+  if (kn.profile && d.last.spec_steps > 0) {
     const sffk::DevCtrl& k = d.last;
     const double sp = (double)k.spec_steps;
     fprintf(stderr, "[sffgpu k_spec_waves leader us/step] publish %.2f first record of the first wave %.2f of the later waves %.2f other records %.2f accepted node %.2f "
@@ -1561,7 +1562,7 @@ void Forest::run_device_seq(int max_waves) {
             k.wprof[0] / sp / 100.0, k.wprof[1] / sp / 100.0, k.wprof[7] / sp / 100.0, k.wprof[2] / sp / 100.0, k.wprof[3] / sp / 100.0, k.wprof[4] / sp / 100.0,
             k.wprof[5] / sp / 100.0, k.wprof[6] / sp / 100.0, (unsigned long long)k.spec_steps, (double)k.spec_committed / sp,
             (double)k.spec_evaluated / (double)std::max<uint64_t>(1, k.spec_committed));
-  } else if (getenv("SFFGPU_PROFILE")) {
+  } else if (kn.profile) {
     const sffk::DevCtrl& k = d.last;
     const double it = (double)std::max(1, k.iter);
     fprintf(stderr, "[sffgpu k_seq_waves us/iteration] pick + node %.2f sample %.2f pose %.2f parent edge %.2f neighbour query %.2f "
@@ -1585,7 +1586,7 @@ void Forest::run_device(int max_waves) {
   // wake-up -> some thirty launches) otherwise leaves the GPU idle for ~40 us per wave.  Everything the device does is
   // self-guarding - after termination or a fault every kernel of the wave behind returns at once - so the wave ahead
   // is harmless when the wave in front ends the run or needs the host.
-  const bool ahead_ok = !getenv("SFFGPU_NO_WAVE_AHEAD");
+  const bool ahead_ok = !kn.no_wave_ahead;
   int slot = 0;          // status slot of the wave the host waits for next
   bool have_next = false;   // a second wave is enqueued behind it (status slot 1 - slot)
   uint64_t started = 0;  // waves enqueued since the last known status (fresh waves the device may have begun)
@@ -1643,7 +1644,7 @@ void Forest::run_device(int max_waves) {
       // the whole wave: 130 ms for a wave of 16 384 slots instead of ~30)
       ++st.host_fallback_waves;
       dev_to_host();
-      const bool whole_wave = getenv("SFFGPU_FALLBACK_WHOLE_WAVE") != nullptr;
+      const bool whole_wave = kn.fallback_whole_wave;
       do {
         round_begin();
         int32_t cnt = (int32_t)records.size();
@@ -1655,7 +1656,7 @@ void Forest::run_device(int max_waves) {
   }
   st.total_ms += ms_since(t0);
   st.host_ms += ms_since(t0) - wait_ms;
-  if (getenv("SFFGPU_PROFILE")) {
+  if (kn.profile) {
     int32_t why[4] = {0, 0, 0, 0};
     HIPCHK(hipMemcpy(why, dev.fault_pending.p, 16, hipMemcpyDeviceToHost));
     {
@@ -1669,7 +1670,7 @@ void Forest::run_device(int max_waves) {
     fprintf(stderr, "[sffgpu samples that sent their round to the host path] hit / neighbour list overflow %d, triangle candidate list %d, walk past a cut neighbour record %d | host fallback waves %llu\n",
             why[1], why[2], why[3], (unsigned long long)st.host_fallback_waves);
   }
-  if (getenv("SFFGPU_PROFILE")) {
+  if (kn.profile) {
     const sffk::DevCtrl& k = d.last;
     {
       const double w = (double)std::max<unsigned long long>(1ULL, k.wprof[7]);

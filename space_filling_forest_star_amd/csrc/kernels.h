@@ -3,6 +3,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "knobs.h"
+
 namespace sffk {
 
 // fp32 SoA node store (the sweep streams these six columns: 24 B per node) plus the
@@ -402,9 +404,9 @@ void launch_classify(hipStream_t s, const ClassifyArgs& a);
 // launch_collide_items
 // returns true when the block kernel (k_query_block) ran: it writes the end points of the edge tasks that left a survivor
 // only and does not clear unused task slots - launch_collide_items then needs `block_src` (the same arguments)
-bool launch_query_classify(hipStream_t s, const GridView& g, const GridView* tg, const NodeStoreView& st,
+bool launch_query_classify(hipStream_t s, const sff::Knobs& kn, const GridView& g, const GridView* tg, const NodeStoreView& st,
                            const SweepQuery* queries, const ClassifyArgs& a, const EnvView* env = nullptr);
-bool query_block_mode(const GridView& g, const GridView* tg, const ClassifyArgs& a, const EnvView* env);
+bool query_block_mode(const sff::Knobs& kn, const GridView& g, const GridView* tg, const ClassifyArgs& a, const EnvView* env);
 // where k_collide_items finds a task's end points when the survivor list ran over after k_query_block
 struct TaskSource {
   const int32_t* rec_nnb; const int32_t* rec_nb; const int32_t* rec_meta; const int32_t* parent;
@@ -413,7 +415,7 @@ struct TaskSource {
 };
 // exact collision work of a round from the survivor list k_query_classify wrote (count in ctrl[2])
 struct TempGridRef;
-void launch_collide_items(hipStream_t s, const EnvView& env, const RobotView& rob, const double* pos6, int n_pose,
+void launch_collide_items(hipStream_t s, const sff::Knobs& kn, const EnvView& env, const RobotView& rob, const double* pos6, int n_pose,
                           const int32_t* live_flags, uint8_t* pose_hit, const double* a6, const double* b6,
                           const int32_t* seg_ns, int stride, int32_t* ctrl, const void* items, int items_cap,
                           const int32_t* sub, int32_t* first_hit, int32_t* overflow_flag, const TempGridRef* temps,
@@ -447,7 +449,7 @@ void launch_seg_prepare(hipStream_t s, const double* a6, const double* b6, int n
 // list = list_cap work items of SFFK_ITEM_BYTES each; masks = list_cap u64 (samples of an item that survive the
 // clearance cull).  An overflowing list only costs speed (the exact kernel then scans the slot table).
 #define SFFK_ITEM_BYTES 64
-void launch_collide_segments_dyn(hipStream_t s, const EnvView& env, const RobotView& rob, const double* a6,
+void launch_collide_segments_dyn(hipStream_t s, const sff::Knobs& kn, const EnvView& env, const RobotView& rob, const double* a6,
                                  const double* b6, const int32_t* seg_ns, int n_slots, int32_t* ctrl,
                                  void* list, int list_cap, void* masks, int32_t* first_hit, int32_t* overflow_flag);
 // a forest round: the same pipeline, and the round's poses go through the cull and the exact kernel with the
@@ -459,7 +461,7 @@ struct TempGridRef {   // the round's own grid + the fp32 coordinates of its n s
 };
 // empties the cells (and occupancy bits) the round's n samples used in the round's own grid
 void launch_tgrid_clear(hipStream_t s, const TempGridRef& t);
-void launch_round_collide(hipStream_t s, const EnvView& env, const RobotView& rob, const double* pos6, int n_pose,
+void launch_round_collide(hipStream_t s, const sff::Knobs& kn, const EnvView& env, const RobotView& rob, const double* pos6, int n_pose,
                           const int32_t* live_flags, uint8_t* pose_hit, const double* a6, const double* b6,
                           const int32_t* seg_ns, int n_slots, int32_t* ctrl, void* list, int list_cap, void* masks,
                           int32_t* first_hit, int32_t* overflow_flag, const TempGridRef* temps,
@@ -706,13 +708,15 @@ struct StarLaunch {            // what the host adds for the SFF* stage of a com
   int tail;                  // the passes after the first as one launch (k_star_tail) instead of one launch per pass
   int tail_wgs;              // ... bound of its grid (0 = one workgroup per CU)
   int tail_stall;            // ... tests: every n-th round one workgroup stays away from the first barrier (the time-out's fault path)
+  int knn_lone;              // the one-wavefront k-nearest kernel (k_star_knn) instead of k_star_knn_wg (Knobs::star_knn)
+  int seg_blocks;            // grid of k_star_exact (0 = its own width; Knobs::seg_blocks)
 };
 void launch_star_stage(hipStream_t s, const ResolveArgs& a, int n_bound, const StarLaunch& L);   // devstar.hip
 // exact collision test of the member-edge chunks a star pass could not answer from the clearance bits (kernels.hip)
 void launch_star_tail(hipStream_t s, const ResolveArgs& a, const EnvView& env, const RobotView& rob, const NodeStoreView& st,
                       int n_bound, int max_passes, int wgs_bound, int test_stall);
 void launch_star_exact(hipStream_t s, const EnvView& env, const RobotView& rob, const double* store_pos, const StarView& S,
-                       int pass);
+                       int pass, int seg_blocks);
 // the commit of one round: k_commit (wide) [-> the SFF* stage] -> k_append / k_append_sample (wide);
 // n_bound = launch bound
 // the arguments of k_sample_steer as one block: the commit's last kernel (k_append_sample) also draws the NEXT round's

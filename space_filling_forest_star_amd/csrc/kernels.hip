@@ -5899,28 +5899,25 @@ void launch_settle(hipStream_t s, const SettleArgs& a) {
 
 // k_query_block serves forests whose buckets are shallow and whose samples see few neighbours (24 exact hits per sample:
 // Forest::query_wide); SFFGPU_QUERY=wide / block overrides the choice
-bool query_block_mode(const GridView& g, const GridView* tg, const ClassifyArgs& a, const EnvView* env) {
-  static const char* const knob = getenv("SFFGPU_QUERY");
+bool query_block_mode(const sff::Knobs& kn, const GridView& g, const GridView* tg, const ClassifyArgs& a, const EnvView* env) {
   if (!env || !g.lite || !g.ovf_lite || !a.qrec || a.nbcap > 16) return false;
   if (a.wide) return false;
   if (tg && tg->cnt && (!tg->lite || !tg->ovf_lite)) return false;
-  if (knob && !strcmp(knob, "wide")) return false;
+  if (kn.query == sff::Knobs::QUERY_WIDE) return false;
   // (the kernel's bucket work list packs a record index into 27 bits)
   if ((long long)g.nx * g.ny * g.nz * g.bk >= (1LL << 27)) return false;
   if (tg && tg->cnt && (long long)tg->nx * tg->ny * tg->nz * tg->bk >= (1LL << 27)) return false;
-  if (knob && !strcmp(knob, "block")) return true;
+  if (kn.query == sff::Knobs::QUERY_BLOCK) return true;
   return g.bk <= 8;
 }
-bool launch_query_classify(hipStream_t s, const GridView& g, const GridView* tg, const NodeStoreView& st,
+bool launch_query_classify(hipStream_t s, const sff::Knobs& kn, const GridView& g, const GridView* tg, const NodeStoreView& st,
                            const SweepQuery* queries, const ClassifyArgs& a, const EnvView* env) {
   if (a.n <= 0) return false;
   GridView none{};
   ClassifyArgs aa = a;
-  if (env) {   // tests shrink the survivor list to drive the exact kernel's table-scan path
-    const int cap_override = getenv("SFFGPU_SEG_LISTCAP") ? atoi(getenv("SFFGPU_SEG_LISTCAP")) : -1;
-    if (cap_override >= 0 && cap_override < aa.items_cap) aa.items_cap = cap_override;
-  }
-  if (query_block_mode(g, tg, a, env)) {
+  // tests shrink the survivor list to drive the exact kernel's table-scan path
+  if (env && kn.seg_listcap >= 0 && kn.seg_listcap < aa.items_cap) aa.items_cap = kn.seg_listcap;
+  if (query_block_mode(kn, g, tg, a, env)) {
     // (the ordered walk: per XCD ceil(perx / 8) sets of 8 sub-ranges x 64 entry numbers, perx = sub-ranges per XCD)
     const int perx_max = (((a.n + 63) / 64) + 7) / 8;
     const int by_sub = 8 * 64 * ((perx_max + 7) / 8);
@@ -5932,7 +5929,7 @@ bool launch_query_classify(hipStream_t s, const GridView& g, const GridView* tg,
                      queries, aa, env ? *env : EnvView{}, env ? 1 : 0);
   return false;
 }
-void launch_collide_items(hipStream_t s, const EnvView& env, const RobotView& rob, const double* pos6, int n_pose,
+void launch_collide_items(hipStream_t s, const sff::Knobs& kn, const EnvView& env, const RobotView& rob, const double* pos6, int n_pose,
                           const int32_t* live_flags, uint8_t* pose_hit, const double* a6, const double* b6,
                           const int32_t* seg_ns, int stride, int32_t* ctrl, const void* items, int items_cap,
                           const int32_t* sub, int32_t* first_hit, int32_t* overflow_flag, const TempGridRef* temps,
@@ -5944,19 +5941,15 @@ void launch_collide_items(hipStream_t s, const EnvView& env, const RobotView& ro
     D.parent = block_src->parent; D.center = block_src->center; D.pos = block_src->pos; D.nbcap = block_src->nbcap;
     D.goal_id = block_src->goal_id;
   }
-  {
-    const int cap_override = getenv("SFFGPU_SEG_LISTCAP") ? atoi(getenv("SFFGPU_SEG_LISTCAP")) : -1;
-    if (cap_override >= 0 && cap_override < items_cap) items_cap = cap_override;
-  }
+  if (kn.seg_listcap >= 0 && kn.seg_listcap < items_cap) items_cap = kn.seg_listcap;
   size_t lds = collide_lds_bytes(rob.n_tri, SEG_WAVES);
   // many-candidate items shared by the workgroup's wavefronts: environments of more than 4 096 triangles (building.obj:
   // 26 908, chunks with 35-130 candidates; dense_3D's 1 832 give 2-8 per item); SFFGPU_SHARE=0 / 1 overrides
-  const char* se = getenv("SFFGPU_SHARE");
-  const bool share = se ? atoi(se) != 0 : env.n_tri > 4096;
+  const bool share = kn.share >= 0 ? kn.share != 0 : env.n_tri > 4096;
   auto kern = share ? k_collide_items<true> : k_collide_items<false>;
   if (lds > 48 * 1024) (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
   // 2 workgroups of 4 waves per CU = what the exact kernel's register budget keeps resident (256 CUs)
-  static const int blocks = std::min(4096, std::max(1, getenv("SFFGPU_SEG_BLOCKS") ? atoi(getenv("SFFGPU_SEG_BLOCKS")) : 256 * CI_OCC));
+  const int blocks = kn.seg_blocks ? kn.seg_blocks : 256 * CI_OCC;
   hipLaunchKernelGGL(kern, dim3(blocks), dim3(64 * SEG_WAVES), lds, s, env, rob, pos6, n_pose, live_flags, pose_hit,
                      a6, b6, seg_ns, stride, ctrl, static_cast<const SurvivorItem*>(items), items_cap, sub, first_hit,
                      overflow_flag,
@@ -5965,10 +5958,10 @@ void launch_collide_items(hipStream_t s, const EnvView& env, const RobotView& ro
 }
 
 void launch_star_exact(hipStream_t s, const EnvView& env, const RobotView& rob, const double* store_pos, const StarView& S,
-                       int pass) {
+                       int pass, int seg_blocks) {
   size_t lds = collide_lds_bytes(rob.n_tri, SEG_WAVES);
   if (lds > 48 * 1024) (void)hipFuncSetAttribute(reinterpret_cast<const void*>(k_star_exact), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-  static const int blocks = std::min(4096, std::max(1, getenv("SFFGPU_SEG_BLOCKS") ? atoi(getenv("SFFGPU_SEG_BLOCKS")) : 256 * CI_OCC));
+  const int blocks = seg_blocks ? seg_blocks : 256 * CI_OCC;
   hipLaunchKernelGGL(k_star_exact, dim3(blocks), dim3(64 * SEG_WAVES), lds, s, env, rob, store_pos, S.ida, S.idb,
                      static_cast<const SurvivorItem*>(S.items), S.items_cap, S.sub + (size_t)pass * SFFK_SUBLISTS * SFFK_STAR_SUB,
                      S.first_hit, S.seg_ovf, S.hdr);
@@ -6031,7 +6024,7 @@ void launch_tgrid_clear(hipStream_t s, const TempGridRef& t) {
 
 // compact -> cull -> exact.  pos6 / pose_hit may be null (edges only); temps (optional) = the round's own grid
 // and the fp32 coordinates of its n_temps samples, emptied by the compaction launch.
-void launch_round_collide(hipStream_t s, const EnvView& env, const RobotView& rob, const double* pos6, int n_pose,
+void launch_round_collide(hipStream_t s, const sff::Knobs& kn, const EnvView& env, const RobotView& rob, const double* pos6, int n_pose,
                           const int32_t* live_flags, uint8_t* pose_hit, const double* a6, const double* b6,
                           const int32_t* seg_ns, int n_slots, int32_t* ctrl, void* list, int list_cap, void* masks,
                           int32_t* first_hit, int32_t* overflow_flag, const TempGridRef* temps, const int32_t* dev_n,
@@ -6041,10 +6034,9 @@ void launch_round_collide(hipStream_t s, const EnvView& env, const RobotView& ro
   size_t lds = collide_lds_bytes(rob.n_tri, SEG_WAVES);
   if (lds > 48 * 1024) (void)hipFuncSetAttribute(reinterpret_cast<const void*>(k_collide_segments_dyn), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
   // 2 workgroups of 4 waves per CU = what the exact kernel's register budget keeps resident (256 CUs)
-  static const int blocks = std::min(4096, std::max(1, getenv("SFFGPU_SEG_BLOCKS") ? atoi(getenv("SFFGPU_SEG_BLOCKS")) : 512));
-  static const int cull_blocks = getenv("SFFGPU_CULL_BLOCKS") ? atoi(getenv("SFFGPU_CULL_BLOCKS")) : 2048;
-  const int cap_override = getenv("SFFGPU_SEG_LISTCAP") ? atoi(getenv("SFFGPU_SEG_LISTCAP")) : -1;  // tests
-  if (cap_override >= 0 && cap_override < list_cap) list_cap = cap_override;
+  const int blocks = kn.seg_blocks ? kn.seg_blocks : 512;
+  const int cull_blocks = kn.cull_blocks;
+  if (kn.seg_listcap >= 0 && kn.seg_listcap < list_cap) list_cap = kn.seg_listcap;  // tests
   if (n_slots > 0)
     hipLaunchKernelGGL(k_seg_compact, dim3((n_slots + 1023) / 1024), dim3(256), 0, s, seg_ns, n_slots, a6, b6, ctrl,
                        static_cast<WorkItem*>(list), list_cap, temps ? temps->tg : GridView{}, temps ? temps->x : nullptr,
@@ -6058,12 +6050,12 @@ void launch_round_collide(hipStream_t s, const EnvView& env, const RobotView& ro
                      static_cast<const unsigned long long*>(masks), first_hit, overflow_flag, dev_n, stride);
 }
 
-void launch_collide_segments_dyn(hipStream_t s, const EnvView& env, const RobotView& rob, const double* a6,
+void launch_collide_segments_dyn(hipStream_t s, const sff::Knobs& kn, const EnvView& env, const RobotView& rob, const double* a6,
                                  const double* b6, const int32_t* seg_ns, int n_slots, int32_t* ctrl,
                                  void* list, int list_cap, void* masks, int32_t* first_hit,
                                  int32_t* overflow_flag) {
   if (n_slots <= 0) return;
-  launch_round_collide(s, env, rob, nullptr, 0, nullptr, nullptr, a6, b6, seg_ns, n_slots, ctrl, list, list_cap, masks,
+  launch_round_collide(s, kn, env, rob, nullptr, 0, nullptr, nullptr, a6, b6, seg_ns, n_slots, ctrl, list, list_cap, masks,
                        first_hit, overflow_flag, nullptr);
 }
 

@@ -21,14 +21,7 @@ namespace sff {
 #define HIPCHK(x) hip_check((x), #x)
 
 Rrt::Rrt(Ctx* c, const sffgpu_rrt_cfg& cf, const double* roots6, int n_roots) : ctx(c), cfg(cf) {
-  if (const char* e = getenv("SFFGPU_RRT_CHAIN")) chain_on = atoi(e) != 0;
-  if (const char* e = getenv("SFFGPU_RRT_FORK")) c->rr_fork = atoi(e) != 0;
-  if (const char* e = getenv("SFFGPU_RRT_REPAIR")) repair_on = atoi(e) != 0;
-  if (const char* e = getenv("SFFGPU_RRT_DRY")) dry_on = atoi(e) != 0;
-  if (const char* e = getenv("SFFGPU_RRT_ONE_CHAIN")) one_chain = atoi(e) != 0;
-  if (const char* e = getenv("SFFGPU_RRT_SPLIT")) split_parts = std::max(1, atoi(e));
-  if (const char* e = getenv("SFFGPU_RRT_SMALL")) { small_cap = std::max(1, atoi(e)); }
-  if (const char* e = getenv("SFFGPU_RRT_GROW")) grow_pct = std::max(100, atoi(e));
+  kn = c->kn = Knobs::from_env();
   if (cfg.dim != 2 && cfg.dim != 6) throw HipError{"rrt: dim must be 2 or 6"};
   if (n_roots < 1) throw HipError{"rrt: at least one root"};
   if (cfg.priority_bias != 0 && !cfg.has_goal) throw HipError{"rrt: goal bias needs a goal (src/main.cpp:330-331)"};
@@ -42,7 +35,7 @@ Rrt::Rrt(Ctx* c, const sffgpu_rrt_cfg& cf, const double* roots6, int n_roots) : 
   links.resize(nt);
   eaten.resize(nt);
   ctx->store_reset(std::max(4096, cfg.max_iterations + nt + 16));
-  if (!getenv("SFFGPU_RRT_NO_GRID")) {
+  if (!kn.rrt_no_grid) {
     // index over the store (the counterpart of flannIndex->buildIndex, src/rrt.h:56-62): used by knn() above
     const double cell = 1.01 * std::max(cfg.sampling_dist, cfg.dist_tree);
     ctx->grid_bk = 8;
@@ -364,7 +357,7 @@ int Rrt::run_wave(int B) {
   std::vector<double> conn_dd;
   bool have_mates = false;
   std::vector<int32_t> mate;
-  if (chain_on && kmax <= 64) {
+  if (kn.rrt_chain && kmax <= 64) {
     // ---- 2-4 as ONE enqueued chain and one wait (Ctx::rrt_chain): the nearest node of the frozen tree (:143), the steered
     // point (:148), its pose and parent edge (:149-151), - RRT* - the k_max nearest store nodes of EVERY new point (:166;
     // those of the points that die in between are thrown away), - several trees - the other trees' nodes around it, and per slot
@@ -374,7 +367,7 @@ int Rrt::run_wave(int B) {
     std::vector<int32_t> tq(B), ni((size_t)B * 2), nc(B), seg((size_t)B * 3), mi((size_t)B * km), mc(B);
     std::vector<uint8_t> hit(B);
     for (int j = 0; j < B; ++j) { memcpy(&q[6 * (size_t)j], w[j].rnd, 48); tq[j] = w[j].tree; }
-    const bool conn_q = tree_frontier.size() > 1 && !getenv("SFFGPU_RRT_NO_CHAIN_CONN");
+    const bool conn_q = tree_frontier.size() > 1 && !kn.rrt_no_chain_conn;
     if (conn_q) { conn_i.resize((size_t)B * conn_cap); conn_dd.resize((size_t)B * conn_cap); conn_c.resize(B); }
     mate.assign(B, -1);
     const bool by_gridk = kmax > 0 && knn_by_grid(tq.data(), B, kmax);
@@ -382,7 +375,7 @@ int Rrt::run_wave(int B) {
     Ctx::RrtRows R1{np.data(), hit.data(), seg.data(), mi.data(), md.data(), mc.data(), conn_i.data(), conn_dd.data(), conn_c.data()};
     // (the repaired rows ride the same chain: the device lists the slots that have a mate - at most alt_cap of them, a slot
     // beyond that ends the wave if it is reached - and evaluates them behind the others)
-    const int alt_cap = one_chain && repair_on ? std::min(B, B / 4 + 32) : 0;
+    const int alt_cap = kn.rrt_one_chain && kn.rrt_repair ? std::min(B, B / 4 + 32) : 0;
     const int acap = std::max(alt_cap, 1);
     std::vector<double> np2((size_t)acap * 6), md2((size_t)acap * km), cd2;
     std::vector<int32_t> seg2((size_t)acap * 3), mi2((size_t)acap * km), mc2(acap), ci2, cc2, d_slot(acap), d_mate(acap);
@@ -464,7 +457,7 @@ int Rrt::run_wave(int B) {
         for (int js = 0; js < B; ++js) {
           const int i = mate[js];
           if (i < 0) continue;
-          if (!repair_on || w[i].pose_hit || !w[i].par_free) { w[js].cut_here = true; continue; }   // (what the device took for alive is not)
+          if (!kn.rrt_repair || w[i].pose_hit || !w[i].par_free) { w[js].cut_here = true; continue; }   // (what the device took for alive is not)
           a_slot.push_back(js); a_mate.push_back(i); a_use.push_back(1);
         }
         seg_rows = (int)a_slot.size();
@@ -506,7 +499,7 @@ int Rrt::run_wave(int B) {
       // alone (a row that is alive becomes a node whatever its other edges say): the replay's walk is done once ahead, dry, and
       // only the rows it takes get member lists, link candidates and edges - nothing past the cut, not both rows of a slot.
       // (Tree merges end the real replay earlier; a row the replay reaches unprepared ends the wave there.)
-      if (dry_on) {
+      if (kn.rrt_dry) {
         std::vector<int> alt_acc;
         std::vector<char> took(w.size(), 0);
         for (int j = 0; j < B; ++j) {
@@ -731,7 +724,7 @@ int Rrt::run_wave(int B) {
   // RRT* waves of some size: the edges go to the GPU in batches - the later batches' lists are built and the earlier
   // batches' rows replayed while the GPU checks the others (Ctx::seg_refs_begin / _end)
   // (two: a batch is a chain of eight launches and copies, ~80 us whatever its size - four batches measured no better)
-  const int n_parts = chained && split_parts > 1 && kmax > 0 && nA >= 64 ? std::min(split_parts, 4) : 1;
+  const int n_parts = chained && kn.rrt_split > 1 && kmax > 0 && nA >= 64 ? std::min(kn.rrt_split, 4) : 1;
   int part_k[5], part_e[5];          // rows / edges where the batches start
   for (int q = 0; q <= n_parts; ++q) part_k[q] = (int)((long long)nA * q / n_parts);
   part_e[0] = 0;
@@ -943,17 +936,17 @@ void Rrt::run(int max_iters) {
     if (cfg.wave <= 0) {
       if (got >= want) B = std::min(4096, B * 2);
       else {
-        // (a cut wave: the next one speculates grow_pct % of what survived; a SMALL wave costs the chain's latency whatever
+        // (a cut wave: the next one speculates kn.rrt_grow % of what survived; a SMALL wave costs the chain's latency whatever
         // its size, so it may as well carry a few times that)
-        const int by_rule = (int)((long long)got * grow_pct / 100) + 1;
-        B = std::max(1, std::min(4096, std::max(by_rule, std::min(small_mul * got + 1, small_cap))));
+        const int by_rule = (int)((long long)got * kn.rrt_grow / 100) + 1;
+        B = std::max(1, std::min(4096, std::max(by_rule, std::min(small_mul * got + 1, kn.rrt_small))));
       }
     }
     if (got == 0 && want > 0 && iter >= cfg.max_iterations) break;
   }
-  if (chain_on) ctx->sync();   // (the last wave's append)
+  if (kn.rrt_chain) ctx->sync();   // (the last wave's append)
   st.total_ms += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
-  if (getenv("SFFGPU_PROFILE")) {
+  if (kn.profile) {
     fprintf(stderr, "[sffgpu rrt run_wave ms] draws %.1f | chain %.1f | repaired slots %.1f | k nearest %.1f | other trees %.1f | edge lists %.1f + edges on the GPU %.1f + results %.1f | replay %.1f | append %.1f  (%llu waves)\n",
             g_rrt_sec[0], g_rrt_sec[1], g_rrt_sec[2], g_rrt_sec[3], g_rrt_sec[4], g_rrt_sec[8], g_rrt_sec[9], g_rrt_sec[5], g_rrt_sec[6], g_rrt_sec[7], (unsigned long long)st.waves);
     fprintf(stderr, "[sffgpu rrt repaired slots] %llu evaluated, %llu taken, %llu waves cut at a slot without one\n", g_rrt_alt[0], g_rrt_alt[1], g_rrt_alt[2]);

@@ -28,7 +28,7 @@ def test_header_declares_and_library_exports_run_batch():
 
 def test_python_binding():
     assert callable(S.run_batch) and "run_batch" in S.__all__
-    assert S.ForestStats._fields_[-1] == ("batch_launches", C.c_uint64)
+    assert S.ForestStats._fields_[-2:] == [("batch_launches", C.c_uint64), ("prio_seq_waves", C.c_uint64)]
     # the header's struct ends with the same member, behind everything that was there before
     src = open(os.path.join(ROOT, "include", "sffgpu.h")).read()
     body = re.sub(r"/\*.*?\*/", "", re.search(r"typedef struct \{([^}]*)\} sffgpu_forest_stats;", src, flags=re.S).group(1), flags=re.S)

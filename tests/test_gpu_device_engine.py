@@ -28,7 +28,7 @@ def ctx(S):
 
 
 class engine:
-    """SFFGPU_ENGINE / test knobs are read when a forest is created"""
+    """every SFFGPU_* knob is read when a forest (context, mesh, session) is created, and never after"""
 
     def __init__(self, **env):
         self.env = {k: str(v) for k, v in env.items()}
@@ -255,7 +255,7 @@ def test_spatial_order_of_the_slots_changes_nothing(S, ctx):
 def test_many_candidate_items_shared_by_the_workgroup_change_nothing(S, ctx):
     """round 5: an exact-kernel item (edge chunk or pose) with many candidate triangles is worked off in blocks by the
     idle wavefronts of its workgroup (share_help in csrc/kernels.hip; environments above 4 096 triangles by default).
-    SFFGPU_SHARE=0 / 1 forces the choice at every launch: same forest - and the oracle's - either way, plain SFF and SFF*."""
+    SFFGPU_SHARE=0 / 1 forces the choice for a forest created under it: same forest - and the oracle's - either way, plain SFF and SFF*."""
     for name, wave, iters, optimize in (("building", 2048, 30000, False), ("building", 1024, 12000, True),
                                         ("dense3d", 1024, 15000, False)):
         fps = []
@@ -295,10 +295,12 @@ def test_waves_of_one_slot_run_as_one_persistent_wavefront(S, ctx):
     assert_same_forest(fo, fg)
     assert fg.stats()["sweeps"] == fo.stats()["iterations"] and fg.stats()["spec_steps"] == 0     # (one round per iteration)
     fp = fg.fingerprint()
+    assert fg.stats()["graph_launches"] == 0                 # (the persistent wavefront replays no wave graph ...
     fg.close()
     with engine(SFFGPU_NO_SEQ=1):                            # the round engine (33 launches per wave) on the same job
         _, fr = make(S, ctx, "dense3d_coarse", 1, 6000, seed=2)
         fr.run()
+    assert fr.stats()["graph_launches"] > 0                  # ... the round engine does: the knob chose the path)
     assert fr.fingerprint() == fp
     fr.close()
     # staged, with a node budget

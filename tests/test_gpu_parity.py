@@ -321,6 +321,7 @@ def test_priority_frontier_mode_on_the_device_engine(S, ctx, name, wave, n_roots
     assert fg.device_engine()
     assert fo.stats()["n_nodes"] > 500
     assert_same_forest(fo, fg)
+    assert fg.stats()["prio_seq_waves"] == 0     # (every wave's picks came from k_prio_plan's plan)
     # (the heaps crowd the samples together: at these small waves a bounded device list runs over now and then and the
     # wave is finished by the host engine - heaps, slots and the wave's pending pushes travel with it)
 
@@ -354,6 +355,8 @@ def test_priority_frontier_mode_sequential_picks(S, ctx, monkeypatch):
     fo, fg = run_pair(S, ctx, "dense3d", 512, 15000, seed=22, n_roots=6, priority_bias=0.95)
     assert fg.device_engine()
     assert_same_forest(fo, fg)
+    st = fg.stats()
+    assert st["prio_seq_waves"] == st["waves"] > 0     # (k_prio_begin's sequential picks ran, in every wave)
 
 
 def test_priority_frontier_mode_staged_runs(S, ctx, monkeypatch):
