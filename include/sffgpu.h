@@ -230,12 +230,25 @@ typedef struct {
   uint64_t waves, speculated, committed;                /* wave engine: launched waves, iterations evaluated / kept */
   uint64_t rng_draws;                                   /* engine words consumed so far (rng_skip included) */
   double lazy_distance;                                 /* lazy_edge: edge->distance (src/lazy.h:262; DBL_MAX unsolved, :280) */
+  uint64_t batch_launches;                              /* launches of the batch kernel (sffgpu_rrt_run_batch) this session took part in */
+  uint64_t batch_host_iterations;                       /* ... and iterations a batch handed to the host path (link + merge, exact ties) */
 } sffgpu_rrt_stats;
 
 typedef struct sffgpu_rrt sffgpu_rrt;
 int sffgpu_rrt_create(sffgpu_ctx* ctx, const sffgpu_rrt_cfg* cfg, const double* roots6, int n_roots, sffgpu_rrt** out);
 void sffgpu_rrt_destroy(sffgpu_rrt* r);
 int sffgpu_rrt_run(sffgpu_rrt* r, int max_iterations); /* 0 = until solved / Problem::maxIterations */
+/* Session batches: n independent RRT / RRT* / Multi-T-RRT sessions advanced together, one wavefront per session, one launch
+ * of the batch kernel per kind (RRT / RRT*) for all of them.  max_iterations means per member what it means for
+ * sffgpu_rrt_run.  Every member ends exactly as sffgpu_rrt_run(r[i], max_iterations) with cfg.wave == 1 would leave it:
+ * nodes, links, merged tree membership, paths, the reference-equivalent counters and rng_draws; waves / speculated /
+ * committed are not touched, batch_launches and batch_host_iterations are.  Members: dim 2 or 6, RRT or RRT*, any root
+ * count, with or without goal and goal bias, any cfg.wave (it only steers sffgpu_rrt_run); NOT lazy_edge sessions; every
+ * member on a context of its own (a context owns one node store), all on one device.  A call that breaks a rule returns
+ * SFFGPU_ERR_ARG before anything runs.  If a member fails, *failed = its index (-1 otherwise) and the message is on ITS
+ * context; every other member has been left after a whole number of launches - consistent, and free to run on, alone or in
+ * a batch.  The statistics' total_ms of every member grows by the wall time of the call. */
+int sffgpu_rrt_run_batch(sffgpu_rrt* const* r, int n, int max_iterations, int32_t* failed /* may be NULL */);
 int sffgpu_rrt_get_stats(sffgpu_rrt* r, sffgpu_rrt_stats* out);
 /* nodes in creation order; tree = the (possibly merged) tree currently holding the node, root_tree = Node::Root */
 int sffgpu_rrt_get_nodes(sffgpu_rrt* r, double* pos6, int32_t* parent, int32_t* tree, int32_t* root_tree,

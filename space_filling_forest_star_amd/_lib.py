@@ -23,7 +23,7 @@ EXPORTED_SYMBOLS = [
     "sffgpu_collide_transforms", "sffgpu_ctx_set_stream", "sffgpu_rccl_unique_id", "sffgpu_ctx_rccl_init", "sffgpu_ctx_set_allgather", "sffgpu_forest_device_engine", "sffgpu_forest_exchange_bytes",
     "sffgpu_forest_rounds_per_wave", "sffgpu_forest_dev_wave_begin", "sffgpu_forest_dev_round_eval",
     "sffgpu_forest_dev_round_commit", "sffgpu_forest_dev_wave_end", "sffgpu_forest_in_wave", "sffgpu_forest_round_begin", "sffgpu_forest_round_records", "sffgpu_forest_round_commit",
-    "sffgpu_forest_run_batch",
+    "sffgpu_forest_run_batch", "sffgpu_rrt_run_batch",
 ]
 
 # sffgpu_allgather_fn: int fn(void* user, const void* send_dev, void* recv_dev, size_t words_i32, void* hip_stream)
@@ -78,7 +78,7 @@ class RrtStats(C.Structure):
                 ("merges", C.c_int32), ("n_links", C.c_int32), ("collide_calls", C.c_uint64),
                 ("path_free_calls", C.c_uint64), ("nn_queries", C.c_uint64), ("total_ms", C.c_double),
                 ("waves", C.c_uint64), ("speculated", C.c_uint64), ("committed", C.c_uint64), ("rng_draws", C.c_uint64),
-                ("lazy_distance", C.c_double)]
+                ("lazy_distance", C.c_double), ("batch_launches", C.c_uint64), ("batch_host_iterations", C.c_uint64)]
 
     def as_dict(self):
         return {k: getattr(self, k) for k, _ in self._fields_}
@@ -150,6 +150,8 @@ def lib():
     L.sffgpu_rrt_create.argtypes = [C.c_void_p, C.POINTER(RrtCfg), c_dp, C.c_int, C.POINTER(C.c_void_p)]
     L.sffgpu_rrt_destroy.argtypes = [C.c_void_p]
     L.sffgpu_rrt_run.argtypes = [C.c_void_p, C.c_int]
+    if hasattr(L, "sffgpu_rrt_run_batch"):   # (SFFGPU_LIB may name a build from before session batches; run_rrt_batch says so)
+        L.sffgpu_rrt_run_batch.argtypes = [C.POINTER(C.c_void_p), C.c_int, C.c_int, c_ip]
     L.sffgpu_rrt_get_stats.argtypes = [C.c_void_p, C.POINTER(RrtStats)]
     L.sffgpu_rrt_get_nodes.argtypes = [C.c_void_p, c_dp, c_ip, c_ip, c_ip, c_ip, c_dp, c_dp]
     L.sffgpu_rrt_get_links.argtypes = [C.c_void_p, c_ip, c_ip, c_ip, c_dp, C.c_int]
@@ -517,6 +519,7 @@ class Rrt:
     def __init__(self, ctx, roots, limits, dist_tree, sampling_dist, dim=6, optimize=False, goal=None,
                  priority_bias=0.0, max_iterations=10000, seed=1, wave=0, lazy_edge=False, rng_skip=0):
         self.ctx = ctx
+        self.lazy_edge = bool(lazy_edge)
         cfg = RrtCfg()
         cfg.wave = wave
         cfg.dim = dim
@@ -812,6 +815,34 @@ def run_batch(forests, max_waves=0):
         elif rc == -1:
             msg += ": not a batch (needs n >= 1 forests with wave == 1, world == 1, the device engine, no goal, no priority_bias," \
                    " at most 64 roots, each on a context of its own, all on one device)"
+        raise SffGpuError(msg)
+
+
+def run_rrt_batch(sessions, max_iterations=0):
+    """Advance independent RRT / RRT* / Multi-T-RRT sessions together (sffgpu_rrt_run_batch): one wavefront per session, one
+    kernel launch per kind for all of them; each session ends exactly as its own run(max_iterations) with wave=1 would leave
+    it.  Every session lives on a context of its own, all on one device.  An error names the member it came from."""
+    sessions = list(sessions)
+    L = lib()
+    if not hasattr(L, "sffgpu_rrt_run_batch"):
+        raise SffGpuError("this build of libsffgpu.so has no sffgpu_rrt_run_batch")
+    arr = (C.c_void_p * max(1, len(sessions)))(*[getattr(r, "h", None) for r in sessions])
+    failed = C.c_int32(-1)
+    rc = L.sffgpu_rrt_run_batch(arr if sessions else None, len(sessions), max_iterations, C.byref(failed))
+    if rc < 0:
+        msg = "sffgpu error %d" % rc
+        if 0 <= failed.value < len(sessions):
+            ctx = sessions[failed.value].ctx
+            msg += " (member %d): %s" % (failed.value, L.sffgpu_last_error(ctx.h).decode())
+        elif rc == -1:
+            bad = [i for i, r in enumerate(sessions) if getattr(r, "h", None) is None or getattr(r, "lazy_edge", False)]
+            seen = {}
+            for i, r in enumerate(sessions):
+                if id(getattr(r, "ctx", None)) in seen and i not in bad:
+                    bad.append(i)
+                seen.setdefault(id(getattr(r, "ctx", None)), i)
+            msg += ": not a session batch%s (needs n >= 1 RRT / RRT* sessions, none of them lazy_edge, none of them twice, each on a" \
+                   " context of its own, all on one device)" % ((", member %d" % min(bad)) if bad else "")
         raise SffGpuError(msg)
 
 

@@ -299,8 +299,38 @@ int sffgpu_rrt_run(sffgpu_rrt* r, int max_iterations) {
   if (!r) return SFFGPU_ERR_ARG;
   GUARD(r->owner, r->r->run(max_iterations));
 }
+int sffgpu_rrt_run_batch(sffgpu_rrt* const* r, int n, int max_iterations, int32_t* failed) {
+  if (failed) *failed = -1;
+  if (!r || n <= 0) return SFFGPU_ERR_ARG;
+  std::vector<Rrt*> members((size_t)n);
+  for (int i = 0; i < n; ++i) {
+    if (!r[i] || r[i]->r->cfg.lazy_edge || !r[i]->r->ctx->grid_on || r[i]->r->ctx->device != r[0]->r->ctx->device) return SFFGPU_ERR_ARG;
+    for (int j = 0; j < i; ++j)   // (a context owns ONE node store: two members of one context - or one session twice - would share it)
+      if (r[j] == r[i] || r[j]->r->ctx == r[i]->r->ctx) return SFFGPU_ERR_ARG;
+    members[(size_t)i] = r[i]->r;
+  }
+  int bad = -1;
+  auto blame = [&](const std::string& msg) {
+    if (bad < 0 || bad >= n) bad = 0;
+    r[bad]->owner->c->err = msg;
+    if (failed) *failed = bad;
+  };
+  try {
+    run_rrt_batch(members.data(), n, max_iterations, &bad);
+  } catch (const HipError& e) {
+    blame(e.msg);
+    return SFFGPU_ERR_HIP;
+  } catch (const std::exception& e) {
+    blame(e.what());
+    return SFFGPU_ERR_STATE;
+  }
+  return SFFGPU_OK;
+}
+// (a session batch may have left the device block ahead of the host mirror the getters read)
+#define RRT_SYNC(r) try { (r)->r->batch_sync_host(); } catch (const HipError& e) { (r)->owner->c->err = e.msg; return SFFGPU_ERR_HIP; }
 int sffgpu_rrt_get_stats(sffgpu_rrt* r, sffgpu_rrt_stats* out) {
   if (!r || !out) return SFFGPU_ERR_ARG;
+  RRT_SYNC(r);
   Rrt& R = *r->r;
   sffgpu_rrt_stats s = R.st;
   s.iterations = R.iter;
@@ -317,6 +347,7 @@ int sffgpu_rrt_get_stats(sffgpu_rrt* r, sffgpu_rrt_stats* out) {
 }
 int sffgpu_rrt_lazy_plan(sffgpu_rrt* r, int32_t* node_ids, int cap) {
   if (!r) return SFFGPU_ERR_ARG;
+  RRT_SYNC(r);
   Rrt& R = *r->r;
   if (R.lazy_last < 0) return 0;
   std::vector<int> chain;
@@ -328,6 +359,7 @@ int sffgpu_rrt_lazy_plan(sffgpu_rrt* r, int32_t* node_ids, int cap) {
 int sffgpu_rrt_get_nodes(sffgpu_rrt* r, double* pos6, int32_t* parent, int32_t* tree, int32_t* root_tree, int32_t* iter,
                          double* cost, double* dist_parent) {
   if (!r) return SFFGPU_ERR_ARG;
+  RRT_SYNC(r);
   Rrt& R = *r->r;
   for (size_t i = 0; i < R.nodes.size(); ++i) {
     const RNode& n = R.nodes[i];
@@ -343,6 +375,7 @@ int sffgpu_rrt_get_nodes(sffgpu_rrt* r, double* pos6, int32_t* parent, int32_t* 
 }
 int sffgpu_rrt_get_links(sffgpu_rrt* r, int32_t* tree, int32_t* n1, int32_t* n2, double* dist, int cap) {
   if (!r) return SFFGPU_ERR_ARG;
+  RRT_SYNC(r);
   int k = 0;
   for (size_t t = 0; t < r->r->links.size(); ++t)
     for (const RLink& l : r->r->links[t]) {
@@ -359,6 +392,7 @@ int sffgpu_rrt_get_links(sffgpu_rrt* r, int32_t* tree, int32_t* n1, int32_t* n2,
 
 int sffgpu_rrt_paths(sffgpu_rrt* r, double* dist, int32_t* connected, int cap_connected) {
   if (!r || !dist) return SFFGPU_ERR_ARG;
+  RRT_SYNC(r);
   Rrt& R = *r->r;
   R.get_paths();
   const int nt = (int)R.trees.size();
@@ -380,6 +414,7 @@ int sffgpu_rrt_path_plan(sffgpu_rrt* r, int i, int j, int32_t* node_ids, int cap
 }
 int sffgpu_rrt_smooth_paths(sffgpu_rrt* r) {
   if (!r) return SFFGPU_ERR_ARG;
+  RRT_SYNC(r);
   Rrt& R = *r->r;
   if (R.nm.empty()) { r->owner->c->err = "rrt smooth_paths: call sffgpu_rrt_paths first"; return SFFGPU_ERR_STATE; }
   try {

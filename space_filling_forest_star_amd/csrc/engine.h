@@ -564,6 +564,41 @@ struct Rrt {
   std::vector<double> pend_pos;       // accepted nodes of the current wave not yet in the device store
   std::vector<int32_t> pend_tree;
   bool defer_append = false;
+
+  // ---- session batches (rrt_batch.cpp): the device block of a session, created on first batch use.  Positions and tree
+  // tags live in the context's store and grid anyway; here the rest of a node (parent, Root, the two distances, iteration),
+  // the live-tree list, the per-tree node counts, a ring of engine words filled from a copy of the session's generator that
+  // runs ahead of it, and the control / status block (sffk::RrtCtrl).
+  //   valid      the block describes the session (possibly further on than the host mirror); any host-side step (run,
+  //              a host iteration) clears it, the next batch uploads again
+  //   host_stale the block is ahead of the host mirror: getters, run and the host iteration call batch_sync_host first
+  struct BatchDev {
+    bool inited = false, valid = false, host_stale = false, ring_pending = false;
+    DevBuf ctrl, parent, root_tree, d_root, d_closest, iter, live, tree_cnt, ring, ktab;
+    PinBuf h_ctrl, h_ring;
+    hipEvent_t ev_ring = nullptr;
+    int node_cap = 0, host_nodes = 0;
+    uint64_t ring_words = 0, produced = 0;   // produced: absolute position of `gen`
+    Mt64 gen;
+    sffk::RrtCtrl last{};
+  } bd;
+  static constexpr int batch_launch_iters = 8192;   // most iterations of one launch (at most 9 engine words each)
+  bool batch_done(int iter0, int max_iters) const;  // nothing left to do for a batch call that began at iteration iter0
+  int batch_iter() const { return bd.valid ? bd.last.iter : iter; }
+  void batch_upload();                               // host mirror -> device block
+  void batch_sync_host();                            // device block -> host mirror, when it is ahead; the Mt64 moves to the cursor
+  void batch_ring_append(const uint64_t* words, size_t n);
+  sffk::RrtSeqArgs batch_prepare(int iters);
+  void batch_take_in();                              // the status block of a launch has come back
+  void batch_host_iteration();                       // the one iteration the kernel handed over, through expand / merge_or_link
+  ~Rrt();
 };
+
+// Session batches (rrt_batch.cpp): n independent RRT / RRT* / Multi-T-RRT sessions, each on a context of its own, advanced in
+// lock step - one wavefront per session, one launch of k_rrt_seq_batch per kind (RRT / RRT*) for all of them - until each is
+// solved, has run Problem::maxIterations or max_iterations more iterations (0 = no bound).  The caller has checked the
+// members (no lazy_edge, distinct contexts, one device).  A member that throws ends the call: *failed = its index, the
+// exception goes on to the caller; every other member has been taken in after a whole number of launches.
+void run_rrt_batch(Rrt* const* members, int n, int max_iterations, int* failed);
 
 }  // namespace sff

@@ -687,6 +687,46 @@ struct SpecArgs {
   unsigned long long* hb;             // debugging (SFFGPU_PROFILE): per worker (step << 8 | phase), [n_sets x n_slots ..]: the leader's last wait; null = off
 };
 void launch_spec_waves(hipStream_t s, const SpecArgs& a);
+// ---- Session batches (k_rrt_seq_batch): n independent RRT / RRT* / Multi-T-RRT sessions in one launch, workgroup b = one
+// wavefront = the one-by-one loop of members_dev[b] (src/rrt.h:93-99 + expandNode :128-322) in the reference's order, every
+// edge checked only when the loop reaches it.  What the loop cannot settle exactly it leaves to the host: the iteration is
+// rolled back to its start (nothing of it was written) and the launch returns with SFFK_RRT_HOST_ITER.
+struct RrtCtrl {                     // control / status block of one session (HBM; copied back after every launch)
+  int32_t n_nodes, iter;             // nodes in the store, iterations run (Rrt::iter)
+  int32_t status, reason;            // SFFK_RRT_* below
+  int32_t grid_ovf, pad0;            // the grid's overflow counter when the launch ended
+  unsigned long long cursor;         // engine words consumed so far (absolute: Mt64::draws)
+  unsigned long long collide_calls, path_free_calls, nn_queries;   // reference-equivalent counters
+};
+#define SFFK_RRT_RAN 0               // the launch ended normally: its iterations, the session's budget or the engine words ran out
+#define SFFK_RRT_HOST_ITER 1         // the next iteration is the host's (Rrt::expand): reason says why
+#define SFFK_RRT_GRID 2              // the grid's overflow list wants the grid re-celled
+#define SFFK_RRT_WHY_LINK 1          // a free edge to another live tree: link + merge (src/rrt.h:233-316)
+#define SFFK_RRT_WHY_TIE 2           // two nodes at exactly one distance in a tree whose list is not in id order
+#define SFFK_RRT_WHY_CAPACITY 3      // node arrays, k beyond the lanes' list, more live trees than lanes
+#define SFFK_RRT_WHY_DEGENERATE 4    // the steered point is not a number (target = nearest node)
+struct RrtSeqArgs {
+  RrtCtrl* ctrl;
+  NodeStoreMut st;
+  GridView g;
+  EnvView env;
+  RobotView rob;
+  int32_t* parent; int32_t* root_tree; double* d_root; double* d_closest; uint32_t* iter;   // per node, beside the store
+  const int32_t* live;                // the live-tree list in frontier order (Rrt::tree_frontier), n_live entries
+  int32_t* tree_cnt;                  // nodes per tree
+  const uint64_t* ring; uint64_t ring_mask;
+  unsigned long long words_end;       // engine words resident in the ring (absolute position)
+  const int32_t* ktab;                // ktab[m] = smallest node count N with (size_t)(2e log10 N) >= m (host libm, src/rrt.h:160)
+  double limits[6], goal[6];
+  double priority_bias, dist_tree, sampling_dist, sweep_abs_eps, cell_edge, knn_slack;
+  int dim, max_iters, iter_limit, node_cap;   // iterations this launch may run; Problem::maxIterations; rows of the node arrays
+  int pick_range, n_live;             // numTrees + 1 (the draw of :95); live trees (the goal's included)
+  int merged;                         // a tree has eaten another: its list is no longer in id order
+  int grid_ovf_limit;
+};
+// All members of a launch are of one kind (optimize: RRT*), lds = the largest collide_lds_bytes(rob.n_tri, 1) among them.
+// Returns the first error of setting the kernel's attribute or of the launch itself.
+hipError_t launch_rrt_seq_batch(hipStream_t s, const RrtSeqArgs* members_dev, int n, bool optimize, size_t lds);
 // the transcendental values of n engine words (3 doubles per word: cos, sin of the word as an angle, acos of it as the pitch draw)
 void launch_ring_trig(hipStream_t s, const uint64_t* words, double* trig, int n);
 // multi-GPU: the answer record of one sample as it travels in the all-gather of a round:

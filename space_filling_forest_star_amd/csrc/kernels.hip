@@ -4493,6 +4493,8 @@ hipError_t launch_seq_waves_batch(hipStream_t s, const SeqArgs* members_dev, int
   return hipGetLastError();
 }
 
+#include "rrt_seq_batch.inc"
+
 void launch_seq_waves(hipStream_t s, const SeqArgs& a) {
 
   const size_t lds = collide_lds_bytes(a.rob.n_tri, 1);

@@ -917,6 +917,8 @@ int Rrt::run_wave(int B) {
 
 void Rrt::run(int max_iters) {
   auto t0 = std::chrono::steady_clock::now();
+  batch_sync_host();                                    // (a session batch may have left the device block ahead of the mirror)
+  if (!(solved || iter == cfg.max_iterations)) bd.valid = false;   // ... and from here on the mirror is ahead of the block
   int done = 0;
   int B = 1;
   while (!(solved || iter == cfg.max_iterations)) {                             // :93
