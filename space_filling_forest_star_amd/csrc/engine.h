@@ -338,6 +338,8 @@ struct DevEngine {
   DevBuf qclk_sh;               // the query kernel's clock bracket, 64 shards (sffk::DevForestView::qclk_sh)
   int spec_n_sc = 0, spec_sets = 0, spec_tm = 0;
   bool spec_off = false;        // SFFGPU_SPEC=0, or a launch stalled (its workgroups were not resident together)
+  uint64_t seq_pick_slack = 0;  // priority frontier in the loop of waves of one slot: extra engine words for the next launch (a pick's
+                                // redraws are not bounded; the launch before ran no wave for want of words - Forest::seq_note_launch)
 };
 
 struct Forest {
@@ -377,6 +379,8 @@ struct Forest {
   // one launch of that loop in two halves (run_device_seq, and run_forest_batch below, which launches many forests at once)
   int seq_launch_waves(int waves_left) const;     // waves the next launch may run (waves_left: the caller's bound, 0 = none)
   uint64_t seq_words_end(int batch) const;         // ... and the ring position its engine words have to reach
+  uint64_t seq_words_per_wave() const;             // engine words budgeted per wave (pick + ThresholdMisses samples)
+  void seq_note_launch(uint64_t waves_before);     // after dev_finish_wave: did the launch get anywhere (priority mode's word slack)
   sffk::SeqArgs seq_prepare(int batch);            // tops the ring up to there, builds the kernel's arguments
   void seq_lists_fault();                          // SFFK_FAULT_LISTS came back: that wave on the host-replay engine, state back up
   bool spec_setup();                // the speculative kernel's scenario tree and buffers; false = k_seq_waves runs the loop

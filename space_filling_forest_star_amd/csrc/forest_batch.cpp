@@ -7,9 +7,10 @@
 //   1. every member that has neither terminated nor run its max_waves is prepared: its engine words are generated (on up
 //      to 16 threads - at 256 members this is the host's largest share), its ring is topped up on its own copy stream, its
 //      SeqArgs are built;
-//   2. per kind (SFF, SFF*: two template instances, so two launches) the members' SeqArgs go up as one array, the kind's
-//      stream waits for the members' ring copies, ONE launch runs all of them, their status blocks are copied back on that
-//      same stream (the first member's of the kind: a step costs one submission per kind, not one per member);
+//   2. per kind (SFF / SFF*, plain / priority frontier: four template instances, so up to four launches) the members'
+//      SeqArgs go up as one array, the kind's stream waits for the members' ring copies, ONE launch runs all of them, their
+//      status blocks are copied back on that same stream (the first member's of the kind: a step costs one submission per
+//      kind, not one per member);
 //   3. one wait per kind;
 //   4. every member is taken in exactly like a single forest: dev_finish_wave (growth, re-celling) and, after a list
 //      fault, that one wave on the host-replay engine (seq_lists_fault).
@@ -33,7 +34,7 @@ using Clock = std::chrono::steady_clock;
 static double ms_since(Clock::time_point t0) { return std::chrono::duration<double, std::milli>(Clock::now() - t0).count(); }
 
 namespace {
-struct ArgBufs {   // the members' SeqArgs: pinned staging + device array, SFF members first
+struct ArgBufs {   // the members' SeqArgs: pinned staging + device array, kind by kind
   PinBuf h;
   DevBuf d;
   ~ArgBufs() { h.release(); d.release(); }
@@ -45,7 +46,9 @@ void run_forest_batch(Forest* const* members, int n, int max_waves, int* failed)
   HIPCHK(hipSetDevice(members[0]->ctx->device));
   const auto t0 = Clock::now();
   double wait_ms = 0;
-  std::vector<uint64_t> w0((size_t)n);
+  std::vector<uint64_t> w0((size_t)n), w_launch((size_t)n, 0);
+  // kind of a member = the template instance that runs it: bit 0 SFF*, bit 1 priority frontier
+  auto kind_of = [&](int i) { return (members[i]->cfg.optimize ? 1 : 0) | (members[i]->use_priority() ? 2 : 0); };
   std::vector<double> alone_ms((size_t)n, 0.0);   // time the member's own run_device(1) calls have already booked
   std::vector<int> waves_now((size_t)n, 0);
   std::vector<std::vector<uint64_t>> words((size_t)n);
@@ -114,14 +117,16 @@ void run_forest_batch(Forest* const* members, int n, int max_waves, int* failed)
         work();
         for (auto& x : th) x.join();
       }
-      // ---- rings and arguments; SFF members in front of SFF* members
+      // ---- rings and arguments; the members kind by kind
       order.clear();
-      for (int kind = 0; kind < 2; ++kind)
-        for (int i : live) if ((members[i]->cfg.optimize ? 1 : 0) == kind) order.push_back(i);
-      const int n_kind[2] = {(int)std::count_if(order.begin(), order.end(), [&](int i) { return !members[i]->cfg.optimize; }),
-                             (int)std::count_if(order.begin(), order.end(), [&](int i) { return members[i]->cfg.optimize != 0; })};
+      int n_kind[4] = {0, 0, 0, 0};
+      size_t first_of[4] = {0, 0, 0, 0};
+      for (int kind = 0; kind < 4; ++kind) {
+        first_of[kind] = order.size();
+        for (int i : live) if (kind_of(i) == kind) { order.push_back(i); ++n_kind[kind]; }
+      }
       sffk::SeqArgs* ha = args.h.as<sffk::SeqArgs>();
-      size_t lds[2] = {0, 0};
+      size_t lds[4] = {0, 0, 0, 0};
       for (size_t s = 0; s < order.size(); ++s) {   // (every member's drawn words reach its ring, whatever happens to another one:
         cur = order[s];                             // a generator ahead of its ring would be an inconsistent forest)
         try {
@@ -132,16 +137,17 @@ void run_forest_batch(Forest* const* members, int n, int max_waves, int* failed)
       for (size_t s = 0; s < order.size(); ++s) {
         cur = order[s];
         Forest& f = *members[cur];
+        w_launch[cur] = f.dev.last.waves;
         ha[s] = f.seq_prepare(waves_now[cur]);
-        const int kind = f.cfg.optimize ? 1 : 0;
+        const int kind = kind_of(cur);
         lds[kind] = std::max(lds[kind], sffk::collide_lds_bytes(ha[s].rob.n_tri, 1));
       }
       // ---- 2. + 3. per kind: arguments up, one launch, the status blocks back - on the stream of the kind's first member
-      bool launched[2] = {false, false};
+      bool launched[4] = {false, false, false, false};
       try {
-        for (int kind = 0; kind < 2; ++kind) {
+        for (int kind = 0; kind < 4; ++kind) {
           if (!n_kind[kind]) continue;
-          const size_t first = kind ? (size_t)n_kind[0] : 0;
+          const size_t first = first_of[kind];
           cur = order[first];
           hipStream_t s = members[cur]->ctx->stream;
           for (size_t j = first; j < first + (size_t)n_kind[kind]; ++j) {
@@ -153,7 +159,7 @@ void run_forest_batch(Forest* const* members, int n, int max_waves, int* failed)
           }
           HIPCHK(hipMemcpyAsync(args.d.as<sffk::SeqArgs>() + first, ha + first, (size_t)n_kind[kind] * sizeof(sffk::SeqArgs),
                                 hipMemcpyHostToDevice, s));
-          HIPCHK(sffk::launch_seq_waves_batch(s, args.d.as<sffk::SeqArgs>() + first, n_kind[kind], kind != 0, lds[kind]));
+          HIPCHK(sffk::launch_seq_waves_batch(s, args.d.as<sffk::SeqArgs>() + first, n_kind[kind], (kind & 1) != 0, (kind & 2) != 0, lds[kind]));
           launched[kind] = true;
           for (size_t j = first; j < first + (size_t)n_kind[kind]; ++j) {
             DevEngine& d = members[order[j]]->dev;
@@ -162,9 +168,9 @@ void run_forest_batch(Forest* const* members, int n, int max_waves, int* failed)
         }
       } catch (...) { fail(cur); }
       const auto tw = Clock::now();
-      for (int kind = 0; kind < 2; ++kind) {
+      for (int kind = 0; kind < 4; ++kind) {
         if (!launched[kind]) continue;
-        cur = order[kind ? (size_t)n_kind[0] : 0];
+        cur = order[first_of[kind]];
         try { HIPCHK(hipStreamSynchronize(members[cur]->ctx->stream)); } catch (...) { fail(cur); launched[kind] = false; }
       }
       wait_ms += ms_since(tw);
@@ -172,12 +178,13 @@ void run_forest_batch(Forest* const* members, int n, int max_waves, int* failed)
       for (size_t s = 0; s < order.size(); ++s) {
         cur = order[s];
         Forest& f = *members[cur];
-        if (!launched[f.cfg.optimize ? 1 : 0]) continue;
+        if (!launched[kind_of(cur)]) continue;
         try {
           f.dev.status_copied[0] = true;
           f.dev.host_stale = true;
           ++f.st.batch_launches;
           const int fault = f.dev_finish_wave(&wait_ms, 0, true);
+          f.seq_note_launch(w_launch[cur]);
           if (fault == SFFK_FAULT_LISTS) f.seq_lists_fault();
           f.ctx->sync();   // (growth, re-celling and the upload run on the member's own stream: done before the next launch)
         } catch (...) { fail(cur); }

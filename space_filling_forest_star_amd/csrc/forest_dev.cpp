@@ -39,9 +39,10 @@ bool Forest::device_eligible() const {
   // mode without a goal (heaps in HBM, one workgroup per heap: devprio.hip); priority + goal runs on the host-replay engine
   if (!use_priority()) return true;
   // (measured on dense_3D, 100 k nodes: 73 k nodes/s at waves of 64 slots against the host engine's 29 k, 0.83 M at 1 024
-  // against 98 k, 1.6 M at 8 192; waves of one slot - the reference's own loop - stay on the host engine;
+  // against 98 k, 1.6 M at 8 192; waves of one slot - the reference's own loop - stay on the host engine unless the forest
+  // was created under SFFGPU_PRIO_LOOP=1, which gives them to the single-wavefront loop (k_seq_waves<., true>);
   // SFFGPU_PRIO_DEVICE=0 keeps the whole mode there)
-  const int min_wave = kn.prio_device ? 2 : 0x7fffffff;
+  const int min_wave = !kn.prio_device ? 0x7fffffff : (kn.prio_loop && !kn.no_seq && num_roots <= 64) ? 1 : 2;
   if (cfg.has_goal || cfg.wave < min_wave || cfg.world > 1) return false;
   const long long heaps_n = (long long)num_roots * (num_roots - 1);
   const long long cap = (long long)std::max(cfg.node_budget, 4096) + 2LL * cfg.wave + 128;
@@ -1330,7 +1331,7 @@ bool Forest::dev_wave_begin() {
 
 // waves of one slot the persistent single-wavefront loop can run (a member of run_forest_batch needs no more) ...
 bool Forest::batch_eligible() const {
-  return dev.on && cfg.wave == 1 && cfg.world == 1 && num_roots <= 64 && !cfg.has_goal && !use_priority();
+  return dev.on && cfg.wave == 1 && cfg.world == 1 && num_roots <= 64 && !cfg.has_goal && (!use_priority() || kn.prio_loop);
 }
 // ... and sffgpu_forest_run takes that loop for them
 bool Forest::seq_eligible() const { return batch_eligible() && !kn.no_seq && !seq_suspended; }
@@ -1343,7 +1344,7 @@ bool Forest::seq_eligible() const { return batch_eligible() && !kn.no_seq && !se
 static const size_t SPEC_HEAD = 4096;   // bytes in front of the records: 4 x 64 control-block granules, the step word
 bool Forest::spec_setup() {
   DevEngine& d = dev;
-  if (d.spec_off) return false;
+  if (d.spec_off || use_priority()) return false;   // (the priority frontier runs on the single wavefront)
   const int TM = std::max(1, cfg.threshold_misses);
   if (d.spec_n_sc > 0 && d.spec_tm == TM) return true;
   if (TM > 8) { d.spec_off = true; return false; }
@@ -1391,16 +1392,30 @@ bool Forest::spec_setup() {
 // ---- the two halves of one launch of the single-wavefront loop, shared by run_device_seq (one forest) and run_forest_batch
 // (forest_batch.cpp: many forests in lock step).  Prepare: how many waves the launch may run, the engine words they may
 // need, the kernel's arguments.  Take in: dev_finish_wave on the status block that came back, then seq_lists_fault.
+// Priority mode: a pick is tree, heap, coin and perhaps an index - and a redraw for every tree / heap found empty, which
+// late in a run are most of them: 2 x trees words on top covers the expected redraws.  Their number is not bounded, so the
+// loop checks the supply per draw; a launch that ran no wave at all for want of words is followed by one with more slack
+// (DevEngine::seq_pick_slack, seq_note_launch).
+uint64_t Forest::seq_words_per_wave() const {
+  return (uint64_t)(8 + (use_priority() ? 2 * num_roots : 0) + std::max(1, cfg.threshold_misses) * (cfg.dim == 2 ? 1 : 6));
+}
+void Forest::seq_note_launch(uint64_t waves_before) {
+  DevEngine& d = dev;
+  if (!use_priority()) return;
+  const sffk::DevCtrl& k = d.last;
+  if (k.waves == waves_before && !k.fault && !k.terminated) d.seq_pick_slack = std::min<uint64_t>(std::max<uint64_t>(64, 2 * d.seq_pick_slack), d.ring_words / 4);
+  else d.seq_pick_slack = 0;
+}
+
 int Forest::seq_launch_waves(int waves_left) const {
-  const uint64_t per_wave = (uint64_t)(8 + std::max(1, cfg.threshold_misses) * (cfg.dim == 2 ? 1 : 6));
+  const uint64_t per_wave = seq_words_per_wave();
   int batch = (int)std::min<uint64_t>(4096, dev.ring_words / (2 * per_wave));
   if (waves_left > 0) batch = std::min(batch, waves_left);
   return batch;
 }
 
 uint64_t Forest::seq_words_end(int batch) const {   // the ring has to hold the words up to this absolute position
-  const uint64_t per_wave = (uint64_t)(8 + std::max(1, cfg.threshold_misses) * (cfg.dim == 2 ? 1 : 6));
-  return dev.last.cursor + (uint64_t)batch * per_wave + 16;
+  return dev.last.cursor + (uint64_t)batch * seq_words_per_wave() + 16 + dev.seq_pick_slack;
 }
 
 sffk::SeqArgs Forest::seq_prepare(int batch) {
@@ -1517,6 +1532,7 @@ void Forest::run_device_seq(int max_waves) {
     HIPCHK(hipEventRecord(d.ev_wave, c.stream));
     d.host_stale = true;
     const int fault = dev_finish_wave(&wait_ms, 0, true);
+    seq_note_launch(waves_before);
     if (trace_path) {
       const size_t nw = (size_t)(d.last.waves - waves_before);
       std::vector<int32_t> tr(nw * 8);

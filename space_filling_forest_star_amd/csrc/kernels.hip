@@ -25,6 +25,7 @@
 #include "sff_geom.h"
 #include "kernels_dev.h"
 #include "star_pass_dev.h"
+#include "prio_heap_dev.h"
 
 namespace sffk {
 
@@ -4460,12 +4461,12 @@ __device__ __attribute__((noinline)) void sq_knn(const GridView& g, const double
 
 // the loop itself is seq_waves_body.inc.  k_seq_waves includes it as text, on its by-value argument, which keeps this entry's
 // code as it was before the loop was shared; seq_waves_body is the same loop as a function of a reference (k_seq_waves_batch)
-template <bool OPT>
+template <bool OPT, bool PRIO>
 __global__ __launch_bounds__(64) void k_seq_waves(SeqArgs A) {
 #include "seq_waves_body.inc"
 }
 
-template <bool OPT>
+template <bool OPT, bool PRIO>
 __device__ __forceinline__ void seq_waves_body(const SeqArgs& A) {
 #include "seq_waves_body.inc"
 }
@@ -4475,36 +4476,40 @@ __device__ __forceinline__ void seq_waves_body(const SeqArgs& A) {
 // local, so they live in scalar registers like the kernel arguments of k_seq_waves do.  A workgroup never waits for another
 // one - no step word, no records, no barrier across the grid - so, unlike k_spec_waves, no grid size can strand a workgroup:
 // what is not resident at once simply runs when a slot frees up.
-template <bool OPT>
+template <bool OPT, bool PRIO>
 __global__ __launch_bounds__(64) void k_seq_waves_batch(const SeqArgs* __restrict__ members, int n) {
   if ((int)blockIdx.x >= n) return;
-  seq_waves_body<OPT>(members[blockIdx.x]);
+  seq_waves_body<OPT, PRIO>(members[blockIdx.x]);
 }
 
-hipError_t launch_seq_waves_batch(hipStream_t s, const SeqArgs* members_dev, int n, bool optimize, size_t lds) {
-  if (n <= 0) return hipSuccess;
-  const void* fn = optimize ? reinterpret_cast<const void*>(k_seq_waves_batch<true>) : reinterpret_cast<const void*>(k_seq_waves_batch<false>);
+template <bool OPT, bool PRIO>
+static hipError_t launch_seq_waves_batch_as(hipStream_t s, const SeqArgs* members_dev, int n, size_t lds) {
   if (lds > 48 * 1024) {
-    const hipError_t e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(k_seq_waves_batch<OPT, PRIO>),
+                                             hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
     if (e != hipSuccess) return e;
   }
-  if (optimize) hipLaunchKernelGGL(k_seq_waves_batch<true>, dim3(n), dim3(64), lds, s, members_dev, n);
-  else hipLaunchKernelGGL(k_seq_waves_batch<false>, dim3(n), dim3(64), lds, s, members_dev, n);
+  hipLaunchKernelGGL((k_seq_waves_batch<OPT, PRIO>), dim3(n), dim3(64), lds, s, members_dev, n);
   return hipGetLastError();
+}
+hipError_t launch_seq_waves_batch(hipStream_t s, const SeqArgs* members_dev, int n, bool optimize, bool priority, size_t lds) {
+  if (n <= 0) return hipSuccess;
+  if (priority) return optimize ? launch_seq_waves_batch_as<true, true>(s, members_dev, n, lds) : launch_seq_waves_batch_as<false, true>(s, members_dev, n, lds);
+  return optimize ? launch_seq_waves_batch_as<true, false>(s, members_dev, n, lds) : launch_seq_waves_batch_as<false, false>(s, members_dev, n, lds);
 }
 
 #include "rrt_seq_batch.inc"
 
+template <bool OPT, bool PRIO>
+static void launch_seq_waves_as(hipStream_t s, const SeqArgs& a, size_t lds) {
+  if (lds > 48 * 1024) (void)hipFuncSetAttribute(reinterpret_cast<const void*>(k_seq_waves<OPT, PRIO>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+  hipLaunchKernelGGL((k_seq_waves<OPT, PRIO>), dim3(1), dim3(64), lds, s, a);
+}
 void launch_seq_waves(hipStream_t s, const SeqArgs& a) {
-
   const size_t lds = collide_lds_bytes(a.rob.n_tri, 1);
-  if (a.optimize) {
-    if (lds > 48 * 1024) (void)hipFuncSetAttribute(reinterpret_cast<const void*>(k_seq_waves<true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    hipLaunchKernelGGL(k_seq_waves<true>, dim3(1), dim3(64), lds, s, a);
-  } else {
-    if (lds > 48 * 1024) (void)hipFuncSetAttribute(reinterpret_cast<const void*>(k_seq_waves<false>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    hipLaunchKernelGGL(k_seq_waves<false>, dim3(1), dim3(64), lds, s, a);
-  }
+  if (a.f.prio.n_heaps > 0) { if (a.optimize) launch_seq_waves_as<true, true>(s, a, lds); else launch_seq_waves_as<false, true>(s, a, lds); }
+  else if (a.optimize) launch_seq_waves_as<true, false>(s, a, lds);
+  else launch_seq_waves_as<false, false>(s, a, lds);
 }
 
 // ------------------------------------------------------------------ waves of one slot, SPECULATED (kernels.h: SpecArgs)

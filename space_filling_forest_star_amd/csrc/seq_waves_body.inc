@@ -5,6 +5,12 @@
 // (310 -> 536 scalar spills, - 3.6 % on its loop, measured); included, both its instances compile to exactly what they were.
 // The batch entry is the other way round: through the function its SFF* instance spills 366 scalars, as included text 517
 // (- 11 %, measured).  Nothing in here looks at the workgroup's index.
+// PRIO (the template parameter beside OPT): the priority-frontier mode of a forest without a goal (src/forest.h:126-147,
+// 160-181, 360-363; PrioView).  The wave's node comes from a heap of a tree (pop / pop at a drawn index), an accepted node
+// is pushed onto every heap of its tree at once, an exhausted node leaves the tree's other heaps, an expanded one goes back
+// onto its own - the heap routines of prio_heap_dev.h, on this one wavefront.  Heap sizes and, per tree, the number of
+// non-empty heaps are kept in LDS (and written through to PrioView::size); the frontier list is not used.  Everything of
+// the mode stands in `if constexpr (PRIO)`: the instances without it compile to what they were.
   extern __shared__ double lds_d[];
   __shared__ int32_t s_fh, s_ovf;
   __shared__ int32_t h_id[64], h_tree[64];
@@ -13,6 +19,8 @@
   DevCtrl* c = f.ctrl;
   const int lane = threadIdx.x;
   if (c->halt || c->in_wave) return;            // (a wave the host left half done goes through the round engine)
+  __shared__ int32_t p_size[PRIO ? SFFK_PRIO_MAX_HEAPS : 1];   // PRIO: entries per heap
+  __shared__ int32_t p_tne[PRIO ? 64 : 1];                     // PRIO: per tree, its non-empty heaps
   double* rtri = lds_d;
   double* stage = rtri + (size_t)A.rob.n_tri * 9;
   int32_t* ibase = reinterpret_cast<int32_t*>(stage + STAGE_DOUBLES);
@@ -37,6 +45,28 @@
   // phase clocks (10 ns ticks): pick + node, sample, pose, parent edge, neighbour query, neighbour loop, append, wave end
   uint64_t pre_w[6] = {0, 0, 0, 0, 0, 0};
   unsigned long long pre_at = ~0ULL;
+  [[maybe_unused]] int total_ne = 0, w_tree = 0, w_heap = -1;   // PRIO: non-empty heaps; the heap the wave's node came from (-1: none)
+  if constexpr (PRIO) {
+    const PrioView& P = f.prio;
+    for (int h = lane; h < P.n_heaps; h += 64) p_size[h] = sq_i32(P.size + h);
+    __builtin_amdgcn_wave_barrier();
+    if (lane < R) {
+      int ne = 0;
+      for (int h = P.base[lane]; h < P.base[lane + 1]; ++h) ne += p_size[h] > 0 ? 1 : 0;
+      p_tne[lane] = ne;
+    }
+    __builtin_amdgcn_wave_barrier();
+    for (int t = 0; t < R; ++t) total_ne += uni_i32(p_tne[t]);
+  }
+  // PRIO: heap h holds n entries from here on (LDS, and the size array the host and the round engine read)
+  [[maybe_unused]] auto p_resize = [&](int t, int h, int was, int n) {
+    if (lane == 0) { p_size[h] = n; f.prio.size[h] = n; }
+    if ((was > 0) != (n > 0)) {
+      if (lane == 0) p_tne[t] += n > 0 ? 1 : -1;
+      total_ne += n > 0 ? 1 : -1;
+    }
+    __builtin_amdgcn_wave_barrier();
+  };
   const bool clk = A.f.profile != 0;   // (a clock read is a scalar memory round trip)
   unsigned long long ph[8] = {0, 0, 0, 0, 0, 0, 0, 0}, tq = clk ? wall_clock64() : 0ULL;
   auto lap = [&](int k) { if (!clk) return; const unsigned long long t = wall_clock64(); ph[k] += t - tq; tq = t; };
@@ -46,13 +76,57 @@
     if ((unsigned long long)(nb + TM) * 2ULL > f.bt_mask + 1ULL) { fault = SFFK_FAULT_BORDER_TABLE; break; }
     if (cursor + 8ULL + (unsigned long long)(TM * WP) > A.words_end) break;      // out of engine words: the host tops the ring up
     if (sq_i32(A.grid_ovf_src) > A.grid_ovf_limit) break;                         // the grid wants to re-cell itself
+    [[maybe_unused]] int hp_node = -1;
+    if constexpr (PRIO) {
+      if (n_nodes + 1 > f.prio.cap) { fault = SFFK_FAULT_INTERNAL; break; }     // (never: a heap holds what the forest can, dev_prio_upload)
+      // ---- node selection, priority frontier (src/forest.h:126-147): a tree with a non-empty heap, a non-empty heap of
+      // it, the coin - every draw checks the word supply (the redraws are not bounded); nothing is popped, and the cursor
+      // stays, unless the whole pick and the wave's attempts have their words
+      w_heap = -1;
+      if (!empty_frontier && total_ne > 0) {
+        const PrioView& P = f.prio;
+        unsigned long long at = cursor;
+        bool dry = false;
+        auto draw = [&](int range) -> int {      // RandGen::randomIntMinMax(0, range - 1); -1 = redraw (or out of words)
+          if (at >= A.words_end) { dry = true; return -1; }
+          const int v = sq_lemire(f.ring[at & f.ring_mask], (unsigned long long)range);
+          ++at;
+          return v;
+        };
+        int t = -1, hp = -1, idx = -1, b0 = 0, size = 0;
+        while (!dry && (t < 0 || uni_i32(p_tne[t]) == 0)) t = draw(R);
+        if (!dry) {
+          b0 = P.base[t];
+          const int nh = P.base[t + 1] - b0;
+          while (!dry && (hp < 0 || uni_i32(p_size[b0 + hp]) == 0)) hp = draw(nh);
+        }
+        if (!dry) {
+          size = uni_i32(p_size[b0 + hp]);
+          if (at >= A.words_end) dry = true;
+          else {
+            const bool top = uniform_real(f.ring[at & f.ring_mask], 0.0, 1.0) <= P.bias;   // :143-147
+            ++at;
+            while (!top && !dry && idx < 0) idx = draw(size);
+          }
+        }
+        if (dry || at + (unsigned long long)(TM * WP) > A.words_end) break;
+        cursor = at;
+        HeapRef hr = heap_with(P, b0 + hp, size);
+        hp_node = idx < 0 ? heap_pop(hr) : heap_pop_at(hr, idx);
+        p_resize(t, b0 + hp, size, size - 1);
+        w_tree = t; w_heap = b0 + hp;
+      }
+    }
     // ---- node selection (src/forest.h:136-151)
-    const int use_closed = cn > 0 && empty_frontier;
+    const int use_closed = (PRIO && w_heap >= 0) ? 0 : (cn > 0 && empty_frontier);
     const int pool = use_closed ? cn : fn;
-    if (pool < 1) { terminated = 1; break; }
-    int pick;
-    do { pick = sq_lemire(f.ring[cursor & f.ring_mask], (unsigned long long)pool); ++cursor; if (pick < 0) ++redraws; } while (pick < 0);
-    const int node = sq_i32((use_closed ? f.closed : frontier) + pick);
+    int pick = 0, node;
+    if (PRIO && w_heap >= 0) node = hp_node;
+    else {
+      if (pool < 1) { terminated = 1; break; }
+      do { pick = sq_lemire(f.ring[cursor & f.ring_mask], (unsigned long long)pool); ++cursor; if (pick < 0) ++redraws; } while (pick < 0);
+      node = sq_i32((use_closed ? f.closed : frontier) + pick);
+    }
     ++waves;
     double cpos[6];
     for (int k = 0; k < 6; ++k) cpos[k] = sq_f64(A.st.pos + 6 * (size_t)node + k);
@@ -297,8 +371,8 @@
         f.d_closest[o] = dcl_new;
         f.d_root[o] = best;
         f.iter[o] = (uint32_t)iter;
-        f.nflag[o] = 2;
-        frontier[fn] = idn;
+        f.nflag[o] = PRIO ? 0 : 2;                 // (PRIO: no frontier list - the tree's heaps, below)
+        if (!PRIO) frontier[fn] = idn;
         if (OPT) {
           atomicAdd(A.tree_cnt + 16 * mine, 1);
           if (A.hist) {
@@ -313,8 +387,21 @@
         grid_put(A.g, it);
       }
       sq_drain();
-      ++n_nodes; ++fn;
+      ++n_nodes;
+      if (!PRIO) ++fn;
       failing = false;
+      if constexpr (PRIO) {   // :360-363 onto every heap of its tree, in heap order
+        const PrioView& P = f.prio;
+        for (int h = P.base[mine]; h < P.base[mine + 1]; ++h) {
+          double ref[6];
+          for (int k = 0; k < 6; ++k) ref[k] = P.ref[6 * (size_t)h + k];
+          const int was = uni_i32(p_size[h]);
+          HeapRef hr = heap_with(P, h, was);
+          heap_push(hr, idn, hk_bits(dist6(qp, ref)));
+          p_resize(mine, h, was, was + 1);
+        }
+        sq_drain();
+      }
       if (OPT) {
         // rewire (:332-350): a member the new node's cost improves, if the edge member -> new is free
         ++st_rounds; st_members += (unsigned long long)n_mem;
@@ -347,7 +434,38 @@
     }
     if (fault) break;
     // ---- the slot is exhausted: its node leaves the frontier for the closed list (:160-178; the erase keeps the order)
-    if (failing && !use_closed) {
+    if constexpr (PRIO) {
+      // (:160-181) a node that came from a heap: exhausted, it leaves the tree's OTHER heaps - where it stands in each comes
+      // from the position maps, a lane per heap - and joins the closed list; expanded, it goes back onto its own heap,
+      // behind the new node's push
+      if (w_heap >= 0) {
+        const PrioView& P = f.prio;
+        if (failing) {
+          const int b0 = P.base[w_tree], nh = P.base[w_tree + 1] - b0;
+          const int at_v = lane < nh ? hl_i32(P.pos + (size_t)(b0 + lane) * P.cap + node) : -1;
+          for (int j = 0; j < nh; ++j) {
+            const int hint = lane_i32(at_v, j);
+            if (b0 + j == w_heap || hint < 0) continue;
+            const int was = uni_i32(p_size[b0 + j]);
+            HeapRef hr = heap_with(P, b0 + j, was);
+            heap_remove(hr, node, hint);
+            p_resize(w_tree, b0 + j, was, hr.n);
+          }
+          const int fl = sq_u8(f.nflag + node);
+          if (!(fl & 1)) {
+            if (lane == 0) { f.nflag[node] = (uint8_t)((fl & ~2) | 1); f.closed[cn] = node; }
+            ++cn;
+          }
+        } else {
+          double ref[6];
+          for (int k = 0; k < 6; ++k) ref[k] = P.ref[6 * (size_t)w_heap + k];
+          const int was = uni_i32(p_size[w_heap]);
+          HeapRef hr = heap_with(P, w_heap, was);
+          heap_push(hr, node, hk_bits(dist6(cpos, ref)));
+          p_resize(w_tree, w_heap, was, was + 1);
+        }
+      }
+    } else if (failing && !use_closed) {
       const int fl = sq_u8(f.nflag + node);
       if (fl & 2) {
         if (lane == 0) { f.nflag[node] = (uint8_t)((fl & ~2) | 1); f.closed[cn] = node; }
@@ -365,7 +483,7 @@
     }
     sq_drain();
     // ---- termination (:184-201)
-    empty_frontier = fn == 0 ? 1 : 0;
+    empty_frontier = PRIO ? (total_ne == 0 ? 1 : 0) : (fn == 0 ? 1 : 0);   // (PRIO: every heap of every tree is empty, :184-191)
     if (!solved && empty_frontier) {
       // maxConnected() == numRoots: every tree reachable from tree 0 over pairs that hold a border (R <= 64: a lane per tree)
       unsigned long long reach = 1ULL, frontier_set = 1ULL;
@@ -403,6 +521,11 @@
     c->fault = fault;
     c->halt = (terminated || fault) ? 1 : 0;
     c->in_wave = in_wave;
+    if constexpr (PRIO) {   // (the loop pushes at acceptance: nothing is pending at any wave's end, or in a wave half done)
+      c->prio_n0 = n_nodes; c->prio_all_empty = total_ne == 0 ? 1 : 0;
+      c->prio_wave = (in_wave && w_heap >= 0) ? 1 : 0;
+      if (in_wave && w_heap >= 0) { f.prio.slot_tree[0] = w_tree; f.prio.slot_heap[0] = w_heap - f.prio.base[w_tree]; }
+    }
     if (in_wave) {   // the state the host engine resumes the wave from: its one slot, still failing, w_round rounds done
       c->round = w_round; c->n_slots = 1; c->use_closed = w_closed; c->act_sel = 0; c->act_cnt = 1;
       f.slot_node[0] = w_node; f.slot_pos[0] = w_pos; f.act_slot[0] = 0;

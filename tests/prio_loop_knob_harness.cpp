@@ -1,0 +1,11 @@
+// Prints Knobs::prio_loop as Knobs::from_env() reads it (tests/test_prio_loop_knob.py compiles this file together with
+// space_filling_forest_star_amd/csrc/knobs.cpp using the host compiler alone).
+#include <cstdio>
+
+#include "knobs.h"
+
+int main() {
+  const sff::Knobs k = sff::Knobs::from_env();
+  printf("prio_loop=%d\n", (int)k.prio_loop);
+  return 0;
+}
