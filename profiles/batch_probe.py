@@ -2,7 +2,8 @@
 (dense_3D, 6-DoF, 10 roots, the scenario's tree / sampling distances, ThresholdMisses 5, node_budget 20 000, seeds 1..B).
 
 Legs (every repeat of every leg is a child process of its own, legs alternated inside one command):
-  a  S.run_batch of the B forests (B contexts)                                         - this build
+  a  S.run_batch of the B forests (B contexts)                                         - this build (--a-builds new,parent:
+                                                                                          and the parent's, alternated)
   b  the B forests one after another through Forest.run (k_spec_waves)                 - the PARENT commit's build
   c  as b with SFFGPU_SPEC=0 (the single-forest k_seq_waves entry, whose body moved)    - the parent's build AND this one
 
@@ -12,6 +13,7 @@ Contexts, mesh uploads and forest creation are outside the timed region; every c
 seeds; the clock is the host's, around calls that end in a synchronisation.  Appends to profiles/batch_probe.jsonl.
 
   python profiles/batch_probe.py --parent-lib /path/to/parent/libsffgpu.so [--kinds sff,star] [--repeats 3]
+  python profiles/batch_probe.py --parent-lib ... --legs a --a-builds new,parent --batch-sizes 64    (one build against another)
 """
 import argparse
 import ctypes as C
@@ -111,6 +113,8 @@ def main():
     ap.add_argument("--batch-sizes", default="")
     ap.add_argument("--seq-sizes", default="")        # leg b; default 1,8,64 (SFF) / 1,64 (SFF*): the rate does not depend on B
     ap.add_argument("--c-size", type=int, default=8)  # leg c
+    ap.add_argument("--legs", default="a,b,c")
+    ap.add_argument("--a-builds", default="new")      # leg a; "new,parent": the parent's run_batch too (a parent that has one)
     ap.add_argument("--child-timeout", type=int, default=420)
     ap.add_argument("--out", default=OUT)
     a = ap.parse_args()
@@ -123,9 +127,10 @@ def main():
         opt = 1 if kind == "star" else 0
         sizes_a = [int(x) for x in a.batch_sizes.split(",")] if a.batch_sizes else ([1, 32, 64] if opt else [1, 8, 32, 64, 128])
         sizes_b = [int(x) for x in a.seq_sizes.split(",")] if a.seq_sizes else ([1, 64] if opt else [1, 8, 64])
-        legs = [("a", "new", B) for B in sizes_a] + [("b", "parent", B) for B in sizes_b]
+        legs = [("a", build, B) for B in sizes_a for build in a.a_builds.split(",")] + [("b", "parent", B) for B in sizes_b]
         if a.c_size > 0:
             legs += [("c", "parent", a.c_size), ("c", "new", a.c_size)]
+        legs = [l for l in legs if l[0] in a.legs.split(",")]
         for rep in range(a.repeats):
             for leg, build, B in legs:
                 env = dict(os.environ)

@@ -3,7 +3,8 @@ bench's job shape (dense_3D, 6-DoF, the scenario's tree / sampling distances, th
 seeds 1..B; 1 root for RRT and RRT*, 10 roots for Multi-T-RRT).
 
 Legs (every repeat of every leg is a child process of its own, legs alternated inside one command):
-  a  S.run_rrt_batch of the B sessions (B contexts)                                     - this build
+  a  S.run_rrt_batch of the B sessions (B contexts)                                     - this build (--a-builds new,parent:
+                                                                                          and the parent's, alternated)
   b  the B sessions one after another through Rrt.run with wave = 0 (speculative waves) - the PARENT commit's build
 
 The parent's build is a libsffgpu.so made from `git archive <parent>` in a directory outside git; --parent-lib names it
@@ -112,6 +113,8 @@ def main():
     ap.add_argument("--repeats", type=int, default=3)
     ap.add_argument("--batch-sizes", default="1,8,32,64")
     ap.add_argument("--seq-sizes", default="")             # leg b; default: the batch sizes (the same B sessions on both sides)
+    ap.add_argument("--legs", default="a,b")
+    ap.add_argument("--a-builds", default="new")           # leg a; "new,parent": the parent's run_rrt_batch too (a parent that has one)
     ap.add_argument("--child-timeout", type=int, default=900)
     ap.add_argument("--out", default=OUT)
     a = ap.parse_args()
@@ -125,8 +128,9 @@ def main():
     for kind in a.kinds.split(","):
         legs = []
         for B in sorted(set(sizes_a) | set(sizes_b)):      # legs alternated: batch, yardstick, batch, ...
-            legs += [("a", "new", B)] if B in sizes_a else []
+            legs += [("a", build, B) for build in a.a_builds.split(",")] if B in sizes_a else []
             legs += [("b", "parent", B)] if B in sizes_b else []
+        legs = [l for l in legs if l[0] in a.legs.split(",")]
         seen = {}
         for rep in range(a.repeats):
             for leg, build, B in legs:

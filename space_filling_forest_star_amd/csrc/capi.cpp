@@ -36,6 +36,40 @@ static std::string g_create_err;
     return SFFGPU_ERR_STATE;                       \
   }
 
+static Forest* engine_of(sffgpu_forest* h) { return h->f; }
+static Rrt* engine_of(sffgpu_rrt* h) { return h->r; }
+
+// sffgpu_forest_run_batch / sffgpu_rrt_run_batch: the members are checked (the family's own predicate; one device, distinct
+// handles, distinct contexts), run(members, &bad) is the lock step, and what it throws is the failed member's error
+template <class Handle, class Eligible, class Run>
+static int run_batch_entry(Handle* const* h, int n, int32_t* failed, Eligible eligible, Run run) {
+  if (failed) *failed = -1;
+  if (!h || n <= 0) return SFFGPU_ERR_ARG;
+  std::vector<decltype(engine_of(h[0]))> members((size_t)n);
+  for (int i = 0; i < n; ++i) {
+    if (!h[i] || !eligible(*engine_of(h[i])) || engine_of(h[i])->ctx->device != engine_of(h[0])->ctx->device) return SFFGPU_ERR_ARG;
+    for (int j = 0; j < i; ++j)   // (a context owns ONE node store: two members of one context - or one member twice - would share it)
+      if (h[j] == h[i] || engine_of(h[j])->ctx == engine_of(h[i])->ctx) return SFFGPU_ERR_ARG;
+    members[(size_t)i] = engine_of(h[i]);
+  }
+  int bad = -1;   // (run_lockstep: whatever it throws, 0 <= bad < n)
+  auto blame = [&](const std::string& msg) {
+    if (bad < 0) bad = 0;
+    h[bad]->owner->c->err = msg;
+    if (failed) *failed = bad;
+  };
+  try {
+    run(members.data(), &bad);
+  } catch (const HipError& e) {
+    blame(e.msg);
+    return SFFGPU_ERR_HIP;
+  } catch (const std::exception& e) {
+    blame(e.what());
+    return SFFGPU_ERR_STATE;
+  }
+  return SFFGPU_OK;
+}
+
 extern "C" {
 
 const char* sffgpu_version(void) { return "sffgpu 0.1 (gfx950)"; }
@@ -163,31 +197,8 @@ int sffgpu_forest_run(sffgpu_forest* f, int max_waves) {
   return f->f->need_host_exchange ? SFFGPU_NEED_HOST_EXCHANGE : SFFGPU_OK;
 }
 int sffgpu_forest_run_batch(sffgpu_forest* const* f, int n, int max_waves, int32_t* failed) {
-  if (failed) *failed = -1;
-  if (!f || n <= 0) return SFFGPU_ERR_ARG;
-  std::vector<Forest*> members((size_t)n);
-  for (int i = 0; i < n; ++i) {
-    if (!f[i] || !f[i]->f->batch_eligible() || f[i]->f->ctx->device != f[0]->f->ctx->device) return SFFGPU_ERR_ARG;
-    for (int j = 0; j < i; ++j)   // (a context owns ONE node store: two members of one context - or one forest twice - would share it)
-      if (f[j] == f[i] || f[j]->f->ctx == f[i]->f->ctx) return SFFGPU_ERR_ARG;
-    members[(size_t)i] = f[i]->f;
-  }
-  int bad = -1;
-  auto blame = [&](const std::string& msg) {
-    if (bad < 0 || bad >= n) bad = 0;
-    f[bad]->owner->c->err = msg;
-    if (failed) *failed = bad;
-  };
-  try {
-    run_forest_batch(members.data(), n, max_waves, &bad);
-  } catch (const HipError& e) {
-    blame(e.msg);
-    return SFFGPU_ERR_HIP;
-  } catch (const std::exception& e) {
-    blame(e.what());
-    return SFFGPU_ERR_STATE;
-  }
-  return SFFGPU_OK;
+  return run_batch_entry(f, n, failed, [](const Forest& m) { return m.batch_eligible(); },
+                         [&](Forest* const* m, int* bad) { run_forest_batch(m, n, max_waves, bad); });
 }
 int sffgpu_rccl_unique_id(uint8_t id128[128]) {
   if (!id128) return SFFGPU_ERR_ARG;
@@ -300,31 +311,8 @@ int sffgpu_rrt_run(sffgpu_rrt* r, int max_iterations) {
   GUARD(r->owner, r->r->run(max_iterations));
 }
 int sffgpu_rrt_run_batch(sffgpu_rrt* const* r, int n, int max_iterations, int32_t* failed) {
-  if (failed) *failed = -1;
-  if (!r || n <= 0) return SFFGPU_ERR_ARG;
-  std::vector<Rrt*> members((size_t)n);
-  for (int i = 0; i < n; ++i) {
-    if (!r[i] || r[i]->r->cfg.lazy_edge || !r[i]->r->ctx->grid_on || r[i]->r->ctx->device != r[0]->r->ctx->device) return SFFGPU_ERR_ARG;
-    for (int j = 0; j < i; ++j)   // (a context owns ONE node store: two members of one context - or one session twice - would share it)
-      if (r[j] == r[i] || r[j]->r->ctx == r[i]->r->ctx) return SFFGPU_ERR_ARG;
-    members[(size_t)i] = r[i]->r;
-  }
-  int bad = -1;
-  auto blame = [&](const std::string& msg) {
-    if (bad < 0 || bad >= n) bad = 0;
-    r[bad]->owner->c->err = msg;
-    if (failed) *failed = bad;
-  };
-  try {
-    run_rrt_batch(members.data(), n, max_iterations, &bad);
-  } catch (const HipError& e) {
-    blame(e.msg);
-    return SFFGPU_ERR_HIP;
-  } catch (const std::exception& e) {
-    blame(e.what());
-    return SFFGPU_ERR_STATE;
-  }
-  return SFFGPU_OK;
+  return run_batch_entry(r, n, failed, [](const Rrt& m) { return !m.cfg.lazy_edge && m.ctx->grid_on; },
+                         [&](Rrt* const* m, int* bad) { run_rrt_batch(m, n, max_iterations, bad); });
 }
 // (a session batch may have left the device block ahead of the host mirror the getters read)
 #define RRT_SYNC(r) try { (r)->r->batch_sync_host(); } catch (const HipError& e) { (r)->owner->c->err = e.msg; return SFFGPU_ERR_HIP; }

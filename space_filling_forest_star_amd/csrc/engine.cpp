@@ -53,6 +53,23 @@ void PinBuf::release() {
   p = nullptr;
   cap = 0;
 }
+void WordRing::init(uint64_t words) {
+  HIPCHK(hipEventCreateWithFlags(&ev_ring, hipEventDisableTiming));
+  ring_words = words;
+  ring.ensure((size_t)words * 8);
+  h_ring.ensure((size_t)words * 8);
+}
+void WordRing::release() {
+  ring.release();
+  h_ring.release();
+  if (ev_ring) (void)hipEventDestroy(ev_ring);
+  ev_ring = nullptr;
+}
+void WordRing::wait_on(hipStream_t s) {
+  if (!ring_pending) return;
+  HIPCHK(hipStreamWaitEvent(s, ev_ring, 0));
+  ring_pending = false;
+}
 
 // ------------------------------------------------------------------ RNG
 void Mt64::reseed(uint64_t seed) {

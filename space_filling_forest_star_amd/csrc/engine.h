@@ -3,6 +3,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include <string.h>
 
 #include <algorithm>
 #include <map>
@@ -56,6 +57,38 @@ struct Mt64 {
   uint64_t next();
   void fill(uint64_t* out, size_t n);          // n consecutive words (same as n calls of next())
   int uniform_int(int lo, int hi);  // uniform_int_distribution<int>(lo,hi) (Lemire multiply-shift)
+};
+
+// Ring of engine words on the device: the words of absolute positions [.., produced) lie at position & (ring_words - 1),
+// copied up from the pinned mirror on the context's copy stream; the stream that reads them waits for the last copy.
+struct WordRing {
+  DevBuf ring;
+  PinBuf h_ring;
+  hipEvent_t ev_ring = nullptr;
+  uint64_t ring_words = 0;      // a power of two
+  uint64_t produced = 0;        // engine words generated so far (absolute position of the generator)
+  bool ring_pending = false;    // a copy has been enqueued that no reading stream has waited for yet
+  void init(uint64_t words);
+  void release();
+  // n words for [produced, produced + n): `words`, or (nullptr) the next n of `gen`.  per_run(at, run) follows the copy of
+  // every contiguous run of ring positions [at, at + run) on copy_stream (the forest's trig table)
+  template <class PerRun = void (*)(uint64_t, size_t)>
+  void append(hipStream_t copy_stream, const uint64_t* words, Mt64* gen, size_t n, PerRun per_run = [](uint64_t, size_t) {}) {
+    uint64_t* hr = h_ring.as<uint64_t>();
+    for (size_t done = 0; done < n;) {
+      const uint64_t at = (produced + done) & (ring_words - 1);
+      const size_t run = std::min<size_t>(n - done, (size_t)(ring_words - at));
+      if (words) memcpy(hr + at, words + done, run * 8);
+      else gen->fill(hr + at, run);
+      hip_check(hipMemcpyAsync(ring.as<uint64_t>() + at, hr + at, run * 8, hipMemcpyHostToDevice, copy_stream), "ring copy");
+      per_run(at, run);
+      done += run;
+    }
+    produced += n;
+    hip_check(hipEventRecord(ev_ring, copy_stream), "ring event");
+    ring_pending = true;
+  }
+  void wait_on(hipStream_t s);  // s reads the ring next: behind the last copy
 };
 
 struct HitRec {
@@ -293,12 +326,12 @@ struct DevEngine {
   bool inited = false;    // fixed-size buffers allocated
   bool active = false;    // the authoritative state currently lives on the device
   bool host_stale = false;// ... and is ahead of the host mirror
-  bool table_dirty = false, ring_pending = false;
+  bool table_dirty = false;
   DevBuf frontier2, rm_words, rm_pref, slot_pos, act_slot2, w_acc, acc_pref, ustate32, wg_pub, commit_seq, kc_trace;
   DevBuf ord_hist, ord_start, ord_key, ord_rank, ord_pos, ord_lst, ord_cnt;
   DevBuf w_ev, ev_h, ev_nb, ev_raw;   // border events of a round, entered by the append launch (sffk::DevForestView)   // spatial order of a wave's slots (sffk::OrderView)
   DevBuf ctrl, parent, d_root, d_closest, iter, nflag, frontier, closed, claim, slot_node, slot_fail, act_slot, b_n1,
-      b_n2, b_ta, b_tb, b_dist, bt_key, bt_val, pair, ring, ulist, d_parent, d_parent2, d_force, fault_pending;
+      b_n2, b_ta, b_tb, b_dist, bt_key, bt_val, pair, ulist, d_parent, d_parent2, d_force, fault_pending;
   // priority-frontier mode on the device (devprio.hip; PrioView in kernels.h)
   DevBuf hp_base, hp_size, hp_v, hp_key, hp_pos, hp_ref, hp_gen, hp_cnt, slot_tree, slot_heap, slot_idx, slot_word, hp_plan;
   int prio_heaps = 0, prio_cap = 0;
@@ -319,13 +352,13 @@ struct DevEngine {
   bool round_timing = false;         // the timing decision of the round being enqueued (evaluation -> commit)
   uint64_t graph_calls[T_KINDS] = {0, 0, 0, 0, 0};   // timed-kernel launches one replay stands for
   uint64_t waves_enqueued = 0, graph_launches = 0, graph_captures = 0;
-  PinBuf h_ctrl, h_ring, h_trig;
+  PinBuf h_ctrl, h_trig;
+  WordRing wr;   // engine words: rng is the generator; in device mode it holds no queue and rng.draws == wr.produced
   DevBuf trig;   // libm parity mode: the C library's cos / sin / acos of every ring word (3 doubles per word)
   bool dev_trig = false;   // waves of one slot without the parity mode: the same table, filled on the device (k_ring_trig)
-  hipEvent_t ev_ring = nullptr, ev_wave = nullptr, ev_wave2 = nullptr;   // (two status slots: one wave may be enqueued ahead)
+  hipEvent_t ev_wave = nullptr, ev_wave2 = nullptr;   // (two status slots: one wave may be enqueued ahead)
   int node_cap = 0, border_cap = 0, temp_base = 0;
-  uint64_t bt_size = 0, ring_words = 0, max_wave_words = 0;
-  uint64_t produced = 0;        // engine words generated so far (absolute position of the generator)
+  uint64_t bt_size = 0, max_wave_words = 0;
   uint64_t rounds_enqueued = 0;
   int host_nodes = 0, host_borders = 0;   // how much of the device arrays the host mirror holds
   sffk::DevCtrl last{};         // status block after the last completed wave
@@ -509,7 +542,7 @@ struct Forest {
   uint64_t fingerprint() const;
 };
 
-// Forest batches (forest_batch.cpp): n independent forests of waves of ONE slot, each on a context of its own, advanced in
+// Forest batches (forest_batch.cpp; the lock step: batch_lockstep.h): n independent forests of waves of ONE slot, each on a context of its own, advanced in
 // lock step - one wavefront per forest, one launch of k_seq_waves_batch per kind (SFF / SFF*) for all of them - until each
 // has terminated or run max_waves waves (0 = no bound).  The caller has checked the members (batch_eligible, distinct
 // contexts, one device).  A member that throws ends the call: *failed = its index, the exception goes on to the caller;
@@ -577,12 +610,11 @@ struct Rrt {
   //              a host iteration) clears it, the next batch uploads again
   //   host_stale the block is ahead of the host mirror: getters, run and the host iteration call batch_sync_host first
   struct BatchDev {
-    bool inited = false, valid = false, host_stale = false, ring_pending = false;
-    DevBuf ctrl, parent, root_tree, d_root, d_closest, iter, live, tree_cnt, ring, ktab;
-    PinBuf h_ctrl, h_ring;
-    hipEvent_t ev_ring = nullptr;
+    bool inited = false, valid = false, host_stale = false;
+    DevBuf ctrl, parent, root_tree, d_root, d_closest, iter, live, tree_cnt, ktab;
+    PinBuf h_ctrl;
     int node_cap = 0, host_nodes = 0;
-    uint64_t ring_words = 0, produced = 0;   // produced: absolute position of `gen`
+    WordRing wr;   // (wr.produced: absolute position of `gen`)
     Mt64 gen;
     sffk::RrtCtrl last{};
   } bd;
@@ -591,14 +623,13 @@ struct Rrt {
   int batch_iter() const { return bd.valid ? bd.last.iter : iter; }
   void batch_upload();                               // host mirror -> device block
   void batch_sync_host();                            // device block -> host mirror, when it is ahead; the Mt64 moves to the cursor
-  void batch_ring_append(const uint64_t* words, size_t n);
   sffk::RrtSeqArgs batch_prepare(int iters);
   void batch_take_in();                              // the status block of a launch has come back
   void batch_host_iteration();                       // the one iteration the kernel handed over, through expand / merge_or_link
   ~Rrt();
 };
 
-// Session batches (rrt_batch.cpp): n independent RRT / RRT* / Multi-T-RRT sessions, each on a context of its own, advanced in
+// Session batches (rrt_batch.cpp; the lock step: batch_lockstep.h): n independent RRT / RRT* / Multi-T-RRT sessions, each on a context of its own, advanced in
 // lock step - one wavefront per session, one launch of k_rrt_seq_batch per kind (RRT / RRT*) for all of them - until each is
 // solved, has run Problem::maxIterations or max_iterations more iterations (0 = no bound).  The caller has checked the
 // members (no lazy_edge, distinct contexts, one device).  A member that throws ends the call: *failed = its index, the

@@ -306,7 +306,7 @@ void Forest::fill_stats(sffgpu_forest_stats* out) {
 Forest::~Forest() {
   DevBuf* bufs[] = {&dev.ctrl, &dev.parent, &dev.d_root, &dev.d_closest, &dev.iter, &dev.nflag, &dev.frontier, &dev.closed,
                     &dev.claim, &dev.slot_node, &dev.slot_fail, &dev.act_slot, &dev.b_n1, &dev.b_n2, &dev.b_ta, &dev.b_tb,
-                    &dev.b_dist, &dev.bt_key, &dev.bt_val, &dev.pair, &dev.ring, &dev.ulist,
+                    &dev.b_dist, &dev.bt_key, &dev.bt_val, &dev.pair, &dev.ulist,
                     &dev.d_parent, &dev.d_parent2, &dev.d_force, &dev.fault_pending, &dev.frontier2, &dev.rm_words, &dev.rm_pref,
                     &dev.slot_pos, &dev.act_slot2, &dev.trig, &dev.s_ktab, &dev.s_tree_cnt, &dev.s_head, &dev.s_mcnt, &dev.s_mid, &dev.s_md,
                     &dev.s_next, &dev.s_prop, &dev.s_best, &dev.s_psel, &dev.s_dcl, &dev.s_cnt, &dev.s_accs, &dev.s_hdr, &dev.s_changed,
@@ -322,10 +322,9 @@ Forest::~Forest() {
   }
   for (DevBuf* b : bufs) b->release();
   dev.h_ctrl.release();
-  dev.h_ring.release();
+  dev.wr.release();
   dev.h_trig.release();
   if (dev.wave_graph) (void)hipGraphExecDestroy(dev.wave_graph);
-  if (dev.ev_ring) (void)hipEventDestroy(dev.ev_ring);
   if (dev.ev_wave) (void)hipEventDestroy(dev.ev_wave);
   if (dev.ev_wave2) (void)hipEventDestroy(dev.ev_wave2);
 }

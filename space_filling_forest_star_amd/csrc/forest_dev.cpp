@@ -327,8 +327,8 @@ sffk::DevForestView Forest::dev_view() const {
   v.bt_val = d.bt_val.as<unsigned long long>();
   v.bt_mask = d.bt_size - 1;
   v.pair = d.pair.as<uint8_t>();
-  v.ring = d.ring.as<uint64_t>();
-  v.ring_mask = d.ring_words - 1;
+  v.ring = d.wr.ring.as<uint64_t>();
+  v.ring_mask = d.wr.ring_words - 1;
   v.node_cap = d.node_cap;
   v.border_cap = d.border_cap;
   v.wave = cfg.wave;
@@ -403,25 +403,18 @@ void Forest::dev_size_border_arrays(int want_cap) {
   }
 }
 
-// ---- engine words: rng is the generator; in device mode it holds no queue and rng.draws == dev.produced
-void Forest::dev_ring_append(const uint64_t* words, size_t n) {   // words for absolute positions [produced, produced + n)
+// ---- engine words: rng is the generator; in device mode it holds no queue and rng.draws == dev.wr.produced
+void Forest::dev_ring_append(const uint64_t* words, size_t n) {   // words for absolute positions [produced, produced + n): given, or the generator's next
   DevEngine& d = dev;
   Ctx& c = *ctx;
-  uint64_t* hr = d.h_ring.as<uint64_t>();
-  size_t done = 0;
-  while (done < n) {
-    const uint64_t at = (d.produced + done) & (d.ring_words - 1);
-    const size_t run = std::min<size_t>(n - done, (size_t)(d.ring_words - at));
-    if (words) memcpy(hr + at, words + done, run * 8);
-    else rng.fill(hr + at, run);
-    HIPCHK(hipMemcpyAsync(d.ring.as<uint64_t>() + at, hr + at, run * 8, hipMemcpyHostToDevice, c.copy_stream));
+  d.wr.append(c.copy_stream, words, &rng, n, [&](uint64_t at, size_t run) {
     if (cfg.libm_sampling) {
       // parity mode: RandGen::randomPointInDistance's transcendental functions (src/randGen.h:78-100) are evaluated
       // HERE, by the C library the reference itself calls.  Which word of the stream becomes which angle is only known on
       // the device (frontier picks and samples share the stream), so every word gets all three values it could be asked
       // for: cos / sin of the word as phi or theta, acos of the word as the pitch draw.
       double* ht = d.h_trig.as<double>() + 3 * at;
-      const uint64_t* hw = hr + at;
+      const uint64_t* hw = d.wr.h_ring.as<uint64_t>() + at;
       const unsigned hw_threads = std::max(1u, std::min(16u, std::thread::hardware_concurrency()));
       const size_t per = (run + hw_threads - 1) / hw_threads;
       auto work = [&](size_t b, size_t e) {
@@ -443,20 +436,16 @@ void Forest::dev_ring_append(const uint64_t* words, size_t n) {   // words for a
       }
       HIPCHK(hipMemcpyAsync(d.trig.as<double>() + 3 * at, ht, run * 24, hipMemcpyHostToDevice, c.copy_stream));
     } else if (d.dev_trig) {
-      sffk::launch_ring_trig(c.copy_stream, d.ring.as<uint64_t>() + at, d.trig.as<double>() + 3 * at, (int)run);
+      sffk::launch_ring_trig(c.copy_stream, d.wr.ring.as<uint64_t>() + at, d.trig.as<double>() + 3 * at, (int)run);
     }
-    done += run;
-  }
-  d.produced += n;
-  HIPCHK(hipEventRecord(d.ev_ring, c.copy_stream));
-  d.ring_pending = true;
+  });
 }
 
 void Forest::dev_ring_top_up(uint64_t cursor, uint64_t ahead) {   // make [cursor, cursor + ahead) resident
   DevEngine& d = dev;
-  if (d.produced >= cursor + ahead) return;
-  const uint64_t need = cursor + ahead - d.produced;
-  if (d.produced + need - cursor > d.ring_words) throw HipError{"forest: engine-word ring too small (internal error)"};
+  if (d.wr.produced >= cursor + ahead) return;
+  const uint64_t need = cursor + ahead - d.wr.produced;
+  if (d.wr.produced + need - cursor > d.wr.ring_words) throw HipError{"forest: engine-word ring too small (internal error)"};
   dev_ring_append(nullptr, (size_t)need);
 }
 
@@ -468,23 +457,21 @@ void Forest::dev_upload_state() {
   const int wave = cfg.wave;
   const int words_per = cfg.dim == 2 ? 1 : 6;
   if (!d.inited) {
-    HIPCHK(hipEventCreateWithFlags(&d.ev_ring, hipEventDisableTiming));
     HIPCHK(hipEventCreateWithFlags(&d.ev_wave, hipEventDisableTiming));
     HIPCHK(hipEventCreateWithFlags(&d.ev_wave2, hipEventDisableTiming));
     // (a slot's pick takes one word - four or so in the priority-frontier mode, whose plan also looks a few words ahead)
     d.max_wave_words = (uint64_t)wave * ((use_priority() ? 5 : 1) + (uint64_t)std::max(1, cfg.threshold_misses) * words_per) + 64;
     // (room for four waves' worth - and for everything the host engine may have generated ahead when the state moves
     // to the device in the middle of a run)
-    d.ring_words = next_pow2(std::max<uint64_t>(4 * d.max_wave_words, (uint64_t)rng_ahead.size() + 2 * d.max_wave_words + 64));
-    if (cfg.wave == 1) d.ring_words = std::max<uint64_t>(d.ring_words, 1 << 18);   // (k_seq_waves: thousands of waves per launch)
-    d.ring.ensure((size_t)d.ring_words * 8);
-    d.h_ring.ensure((size_t)d.ring_words * 8);
+    uint64_t ring_words = next_pow2(std::max<uint64_t>(4 * d.max_wave_words, (uint64_t)rng_ahead.size() + 2 * d.max_wave_words + 64));
+    if (cfg.wave == 1) ring_words = std::max<uint64_t>(ring_words, 1 << 18);   // (k_seq_waves: thousands of waves per launch)
+    d.wr.init(ring_words);
     if (cfg.libm_sampling) {
-      d.trig.ensure((size_t)d.ring_words * 24);
-      d.h_trig.ensure((size_t)d.ring_words * 24);
+      d.trig.ensure((size_t)d.wr.ring_words * 24);
+      d.h_trig.ensure((size_t)d.wr.ring_words * 24);
     } else if (cfg.wave == 1 && !kn.no_dev_trig) {
       // waves of one slot: the one wavefront that is waited for looks its sample's cos / sin / acos up (k_ring_trig fills the table)
-      d.trig.ensure((size_t)d.ring_words * 24);
+      d.trig.ensure((size_t)d.wr.ring_words * 24);
       d.dev_trig = true;
     }
     d.ctrl.ensure(sizeof(sffk::DevCtrl));
@@ -595,14 +582,14 @@ void Forest::dev_upload_state() {
   // engine words: what the host generated ahead moves into the ring, the generator continues behind it
   {
     const uint64_t cursor = rng.draws;
-    d.produced = cursor;
+    d.wr.produced = cursor;
     const size_t left = rng.qn - rng.qh;
     std::vector<uint64_t> ahead(rng.q ? rng.q + rng.qh : nullptr, rng.q ? rng.q + rng.qn : nullptr);
     rng.q = nullptr;
     rng.qh = rng.qn = 0;
-    if (left) dev_ring_append(ahead.data(), std::min<size_t>(left, (size_t)d.ring_words));
-    if (left > d.ring_words) throw HipError{"forest: look-ahead queue larger than the engine-word ring"};
-    rng.draws = d.produced;
+    if (left) dev_ring_append(ahead.data(), std::min<size_t>(left, (size_t)d.wr.ring_words));
+    if (left > d.wr.ring_words) throw HipError{"forest: look-ahead queue larger than the engine-word ring"};
+    rng.draws = d.wr.produced;
     sffk::DevCtrl k{};
     k.status_seq = (int32_t)d.status_next;   // (the ring's numbering goes on)
     k.n_nodes = n;
@@ -810,11 +797,11 @@ void Forest::dev_to_host() {
   Ctx& c = *ctx;
   HIPCHK(hipStreamSynchronize(c.copy_stream));
   const uint64_t cursor = d.last.cursor;
-  const size_t left = (size_t)(d.produced - cursor);
+  const size_t left = (size_t)(d.wr.produced - cursor);
   const size_t keep = std::max(rng_ahead.size(), left + 16);
   std::vector<uint64_t> buf(keep, 0);
-  const uint64_t* hr = d.h_ring.as<uint64_t>();
-  for (size_t j = 0; j < left; ++j) buf[j] = hr[(cursor + j) & (d.ring_words - 1)];
+  const uint64_t* hr = d.wr.h_ring.as<uint64_t>();
+  for (size_t j = 0; j < left; ++j) buf[j] = hr[(cursor + j) & (d.wr.ring_words - 1)];
   rng_ahead.swap(buf);
   rng.q = rng_ahead.data();
   rng.qh = 0;
@@ -910,10 +897,7 @@ size_t Forest::dev_exchange_bytes() const {   // what one rank contributes to th
 void Forest::dev_enqueue_begin() {
   Ctx& c = *ctx;
   DevEngine& d = dev;
-  if (d.ring_pending) {   // the words this wave may read have to be resident
-    HIPCHK(hipStreamWaitEvent(c.stream, d.ev_ring, 0));
-    d.ring_pending = false;
-  }
+  d.wr.wait_on(c.stream);   // the words this wave may read have to be resident
   sffk::launch_wave_begin(c.stream, dev_view());
 }
 
@@ -1137,7 +1121,7 @@ uint64_t Forest::dev_launch_signature() {
   mix(&c.envv, sizeof c.envv);
   mix(&c.robv, sizeof c.robv);
   const void* ptrs[] = {c.r_q.p, c.r_cnt.p, c.r_sega.p, c.r_segb.p, c.r_items.p, c.r_sub.p, c.r_out.p, c.r_center.p, c.r_qrec.p, dev.d_parent.p, dev.d_force.p,
-                        dev.ctrl.p, dev.ring.p, dev.trig.p, c.sx.p, c.spos.p, c.stree.p};
+                        dev.ctrl.p, dev.wr.ring.p, dev.trig.p, c.sx.p, c.spos.p, c.stree.p};
   mix(ptrs, sizeof ptrs);
   const double scal[] = {c.sweep_eps(), c.grid_cell, cfg.sampling_dist, cfg.dist_tree};
   mix(scal, sizeof scal);
@@ -1168,10 +1152,7 @@ void Forest::dev_enqueue_wave_kernels(bool sharded, size_t words) {
 void Forest::dev_enqueue_wave(int slot) {
   Ctx& c = *ctx;
   DevEngine& d = dev;
-  if (d.ring_pending) {   // the words this wave may read have to be resident
-    HIPCHK(hipStreamWaitEvent(c.stream, d.ev_ring, 0));
-    d.ring_pending = false;
-  }
+  d.wr.wait_on(c.stream);   // the words this wave may read have to be resident
   // (SFFGPU_TEST_EXCHANGE_SELF: a one-rank forest packs, all-gathers and unpacks too - the collective on one GPU)
   const bool self_exchange = kn.test_exchange_self;
   const bool sharded = cfg.world > 1 || (self_exchange && (ctx->rccl_comm != nullptr || ctx->xchg_fn != nullptr));
@@ -1403,13 +1384,13 @@ void Forest::seq_note_launch(uint64_t waves_before) {
   DevEngine& d = dev;
   if (!use_priority()) return;
   const sffk::DevCtrl& k = d.last;
-  if (k.waves == waves_before && !k.fault && !k.terminated) d.seq_pick_slack = std::min<uint64_t>(std::max<uint64_t>(64, 2 * d.seq_pick_slack), d.ring_words / 4);
+  if (k.waves == waves_before && !k.fault && !k.terminated) d.seq_pick_slack = std::min<uint64_t>(std::max<uint64_t>(64, 2 * d.seq_pick_slack), d.wr.ring_words / 4);
   else d.seq_pick_slack = 0;
 }
 
 int Forest::seq_launch_waves(int waves_left) const {
   const uint64_t per_wave = seq_words_per_wave();
-  int batch = (int)std::min<uint64_t>(4096, dev.ring_words / (2 * per_wave));
+  int batch = (int)std::min<uint64_t>(4096, dev.wr.ring_words / (2 * per_wave));
   if (waves_left > 0) batch = std::min(batch, waves_left);
   return batch;
 }
@@ -1434,7 +1415,7 @@ sffk::SeqArgs Forest::seq_prepare(int batch) {
   a.sampling_dist = cfg.sampling_dist;
   a.sweep_abs_eps = c.sweep_eps();
   a.trig = (cfg.libm_sampling || d.dev_trig) ? d.trig.as<double>() : nullptr;
-  a.words_end = d.produced;
+  a.words_end = d.wr.produced;
   a.grid_ovf_src = c.gridv.ovf_cnt;
   a.dim = cfg.dim;
   a.max_waves = batch;
@@ -1492,10 +1473,7 @@ void Forest::run_device_seq(int max_waves) {
     }
     const int batch = seq_launch_waves(max_waves > 0 ? max_waves - (int)(k.waves - w0) : 0);
     sffk::SeqArgs a = seq_prepare(batch);
-    if (d.ring_pending) {
-      HIPCHK(hipStreamWaitEvent(c.stream, d.ev_ring, 0));
-      d.ring_pending = false;
-    }
+    d.wr.wait_on(c.stream);
     const char* trace_path = kn.seq_trace.empty() ? nullptr : kn.seq_trace.c_str();
     DevBuf trace_buf;
     if (trace_path) {

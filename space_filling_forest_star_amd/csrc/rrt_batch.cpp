@@ -3,42 +3,30 @@
 // One session one iteration at a time (src/rrt.h:93-99) keeps one wavefront busy and nothing else; independent sessions
 // need neither speculation nor co-residency: k_rrt_seq_batch gives every member a wavefront of its own that runs the
 // reference's loop - nearest node, steer, pose and parent edge, the other live trees, RRT* choose-parent / rewire, append -
-// with every edge checked only when the loop reaches it.  A step of the lock step:
-//   1. every member that still has iterations to run is prepared: an iteration the kernel handed over (link + merge, an
-//      exact tie in a merged tree's list, a capacity) runs alone through Rrt::expand and the device block is uploaded again;
-//      its engine words are generated from the block's own copy of the generator (on up to 16 threads), its ring is topped
-//      up on its own copy stream, its RrtSeqArgs are built;
-//   2. per kind (RRT, RRT*: two template instances, so two launches) the members' arguments go up as one array, the kind's
-//      stream waits for the members' ring copies, ONE launch runs all of them, their status blocks are copied back on that
-//      same stream;
-//   3. one wait per kind;
-//   4. every member is taken in: node count of the store, the grid re-celled when its overflow list asks for it.
+// with every edge checked only when the loop reaches it.  The lock step itself is run_lockstep (batch_lockstep.h); here is
+// what is a session's own in it:
+//   - a member is live while it has iterations to run; an iteration the kernel handed over (link + merge, an exact tie in a
+//     merged tree's list, a capacity) runs alone through Rrt::expand first and the device block is uploaded again;
+//   - its engine words come from the block's own copy of the generator;
+//   - two kinds (RRT, RRT*: the template instances of the kernel), at most batch_launch_iters iterations a launch;
+//   - a member is taken in: node count of the store, the grid re-celled when its overflow list asks for it.
 // The host mirror (nodes, tree lists, counters, the Mt64) is refreshed lazily (batch_sync_host): by the getters, by
 // sffgpu_rrt_run and by the host iteration.
-#include <algorithm>
-#include <atomic>
-#include <chrono>
 #include <cmath>
 #include <cstring>
-#include <exception>
-#include <thread>
-#include <vector>
 
-#include "engine.h"
+#include "batch_lockstep.h"
 
 namespace sff {
 
 #define HIPCHK(x) hip_check((x), #x)
-using Clock = std::chrono::steady_clock;
-static double ms_since(Clock::time_point t0) { return std::chrono::duration<double, std::milli>(Clock::now() - t0).count(); }
 
 Rrt::~Rrt() {
   BatchDev& d = bd;
-  DevBuf* bufs[] = {&d.ctrl, &d.parent, &d.root_tree, &d.d_root, &d.d_closest, &d.iter, &d.live, &d.tree_cnt, &d.ring, &d.ktab};
+  DevBuf* bufs[] = {&d.ctrl, &d.parent, &d.root_tree, &d.d_root, &d.d_closest, &d.iter, &d.live, &d.tree_cnt, &d.ktab};
   for (DevBuf* b : bufs) b->release();
   d.h_ctrl.release();
-  d.h_ring.release();
-  if (d.ev_ring) (void)hipEventDestroy(d.ev_ring);
+  d.wr.release();
 }
 
 bool Rrt::batch_done(int iter0, int max_iters) const {
@@ -57,10 +45,7 @@ void Rrt::batch_upload() {
   c.grid_insert_new();
   c.grid_check();
   if (!d.inited) {
-    HIPCHK(hipEventCreateWithFlags(&d.ev_ring, hipEventDisableTiming));
-    d.ring_words = 1u << 17;   // (>= batch_launch_iters x 9 words + slack)
-    d.ring.ensure((size_t)d.ring_words * 8);
-    d.h_ring.ensure((size_t)d.ring_words * 8);
+    d.wr.init(1u << 17);   // (>= batch_launch_iters x 9 words + slack)
     d.ctrl.ensure(sizeof(sffk::RrtCtrl));
     d.h_ctrl.ensure(sizeof(sffk::RrtCtrl));
     // k = (size_t)(2e log10(#nodes)) (src/rrt.h:160): the node counts at which it steps, found with the C library's log10 in
@@ -116,8 +101,8 @@ void Rrt::batch_upload() {
   d.last = k;
   // the ring starts over at the generator's position: a copy of it runs ahead, the session's own moves when the mirror does
   d.gen = rng;
-  d.produced = rng.draws;
-  d.ring_pending = false;
+  d.wr.produced = rng.draws;
+  d.wr.ring_pending = false;
   d.host_nodes = (int)n;
   d.valid = true;
   d.host_stale = false;
@@ -172,23 +157,6 @@ void Rrt::batch_sync_host() {
   d.host_stale = false;
 }
 
-void Rrt::batch_ring_append(const uint64_t* words, size_t n) {   // words for absolute positions [produced, produced + n)
-  BatchDev& d = bd;
-  Ctx& c = *ctx;
-  uint64_t* hr = d.h_ring.as<uint64_t>();
-  size_t done = 0;
-  while (done < n) {
-    const uint64_t at = (d.produced + done) & (d.ring_words - 1);
-    const size_t run = std::min<size_t>(n - done, (size_t)(d.ring_words - at));
-    memcpy(hr + at, words + done, run * 8);
-    HIPCHK(hipMemcpyAsync(d.ring.as<uint64_t>() + at, hr + at, run * 8, hipMemcpyHostToDevice, c.copy_stream));
-    done += run;
-  }
-  d.produced += n;
-  HIPCHK(hipEventRecord(d.ev_ring, c.copy_stream));
-  d.ring_pending = true;
-}
-
 sffk::RrtSeqArgs Rrt::batch_prepare(int iters) {
   Ctx& c = *ctx;
   BatchDev& d = bd;
@@ -206,9 +174,9 @@ sffk::RrtSeqArgs Rrt::batch_prepare(int iters) {
   a.iter = d.iter.as<uint32_t>();
   a.live = d.live.as<int32_t>();
   a.tree_cnt = d.tree_cnt.as<int32_t>();
-  a.ring = d.ring.as<uint64_t>();
-  a.ring_mask = d.ring_words - 1;
-  a.words_end = d.produced;
+  a.ring = d.wr.ring.as<uint64_t>();
+  a.ring_mask = d.wr.ring_words - 1;
+  a.words_end = d.wr.produced;
   a.ktab = d.ktab.as<int32_t>();
   memcpy(a.limits, cfg.limits, sizeof a.limits);
   memcpy(a.goal, cfg.goal, sizeof a.goal);
@@ -260,132 +228,47 @@ void Rrt::batch_host_iteration() {
 }
 
 namespace {
-struct RrtArgBufs {   // the members' RrtSeqArgs: pinned staging + device array, RRT members first
-  PinBuf h;
-  DevBuf d;
-  ~RrtArgBufs() { h.release(); d.release(); }
+struct RrtFamily {
+  using Args = sffk::RrtSeqArgs;
+  static constexpr int n_kinds = 2;   // RRT, RRT*
+  Rrt* const* m;
+  int n, max_iterations;
+  std::vector<int> iter0;
+
+  int device() { return m[0]->ctx->device; }
+  void begin(int i) { iter0[i] = m[i]->batch_iter(); }
+  int plan(int i) {
+    Rrt& r = *m[i];
+    // (an iteration the kernel handed over: alone, through the host path - then the block goes up again)
+    while (!r.batch_done(iter0[i], max_iterations) && r.bd.valid && r.bd.last.status == SFFK_RRT_HOST_ITER) r.batch_host_iteration();
+    if (r.batch_done(iter0[i], max_iterations)) return 0;
+    if (!r.bd.valid) r.batch_upload();
+    int left = r.cfg.max_iterations - r.bd.last.iter;
+    if (max_iterations > 0) left = std::min(left, max_iterations - (r.bd.last.iter - iter0[i]));
+    return std::min(left, Rrt::batch_launch_iters);
+  }
+  uint64_t words_needed(int i, int iters) {
+    const Rrt::BatchDev& d = m[i]->bd;
+    const uint64_t ahead = (uint64_t)iters * 9 + 16, end = d.last.cursor + ahead;
+    if (ahead > d.wr.ring_words) throw HipError{"rrt batch: engine-word ring too small (internal error)"};
+    return end > d.wr.produced ? end - d.wr.produced : 0;
+  }
+  Mt64& gen(int i) { return m[i]->bd.gen; }
+  void ring_append(int i, const uint64_t* w, size_t nw) { m[i]->bd.wr.append(m[i]->ctx->copy_stream, w, nullptr, nw); }
+  WordRing& ring(int i) { return m[i]->bd.wr; }
+  Args prepare(int i, int iters) { return m[i]->batch_prepare(iters); }
+  int kind(int i) { return m[i]->cfg.optimize ? 1 : 0; }
+  hipStream_t stream(int i) { return m[i]->ctx->stream; }
+  StatusBlock status(int i) { return {m[i]->bd.h_ctrl.p, m[i]->bd.ctrl.p, sizeof(sffk::RrtCtrl)}; }
+  hipError_t launch(hipStream_t s, const Args* a, int count, int kind, size_t lds) { return sffk::launch_rrt_seq_batch(s, a, count, kind != 0, lds); }
+  void take_in(int i, double*) { m[i]->batch_take_in(); }
+  void finish(double wall, double) { for (int i = 0; i < n; ++i) m[i]->st.total_ms += wall; }
 };
 }  // namespace
 
 void run_rrt_batch(Rrt* const* members, int n, int max_iterations, int* failed) {
-  *failed = -1;
-  HIPCHK(hipSetDevice(members[0]->ctx->device));
-  const auto t0 = Clock::now();
-  std::vector<int> iter0((size_t)n), iters_now((size_t)n, 0);
-  std::vector<std::vector<uint64_t>> words((size_t)n);
-  std::vector<int> live, order;
-  RrtArgBufs args;
-  args.h.ensure((size_t)n * sizeof(sffk::RrtSeqArgs));
-  args.d.ensure((size_t)n * sizeof(sffk::RrtSeqArgs));
-  std::exception_ptr err;
-  auto fail = [&](int i) { if (!err) { err = std::current_exception(); *failed = i; } };
-  int cur = 0;
-  try {
-    for (cur = 0; cur < n; ++cur) iter0[cur] = members[cur]->batch_iter();
-    while (true) {
-      // ---- 1. who takes part, and for how many iterations
-      live.clear();
-      for (cur = 0; cur < n; ++cur) {
-        Rrt& r = *members[cur];
-        // (an iteration the kernel handed over: alone, through the host path - then the block goes up again)
-        while (!r.batch_done(iter0[cur], max_iterations) && r.bd.valid && r.bd.last.status == SFFK_RRT_HOST_ITER) r.batch_host_iteration();
-        if (r.batch_done(iter0[cur], max_iterations)) continue;
-        if (!r.bd.valid) r.batch_upload();
-        int left = r.cfg.max_iterations - r.bd.last.iter;
-        if (max_iterations > 0) left = std::min(left, max_iterations - (r.bd.last.iter - iter0[cur]));
-        iters_now[cur] = std::min(left, Rrt::batch_launch_iters);
-        live.push_back(cur);
-      }
-      if (live.empty()) break;
-      // ---- the engine words the launch may need, from every member's own generator: pure host work, on up to 16 threads
-      uint64_t short_total = 0;
-      for (int i : live) {
-        Rrt& r = *members[i];
-        const uint64_t end = r.bd.last.cursor + (uint64_t)iters_now[i] * 9 + 16;
-        if (end - r.bd.last.cursor > r.bd.ring_words) throw HipError{"rrt batch: engine-word ring too small (internal error)"};
-        words[i].resize(end > r.bd.produced ? (size_t)(end - r.bd.produced) : 0);
-        short_total += words[i].size();
-      }
-      {
-        std::atomic<size_t> next{0};
-        auto work = [&]() {
-          for (size_t j = next++; j < live.size(); j = next++) {
-            Rrt& r = *members[live[j]];
-            if (!words[live[j]].empty()) r.bd.gen.fill(words[live[j]].data(), words[live[j]].size());
-          }
-        };
-        const unsigned nt = short_total < (1u << 16) ? 1u
-                            : std::max(1u, std::min({16u, std::thread::hardware_concurrency(), (unsigned)live.size()}));
-        std::vector<std::thread> th;
-        for (unsigned t = 1; t < nt; ++t) th.emplace_back(work);
-        work();
-        for (auto& x : th) x.join();
-      }
-      // ---- rings and arguments; RRT members in front of RRT* members
-      order.clear();
-      for (int kind = 0; kind < 2; ++kind)
-        for (int i : live) if ((members[i]->cfg.optimize ? 1 : 0) == kind) order.push_back(i);
-      const int n_kind[2] = {(int)std::count_if(order.begin(), order.end(), [&](int i) { return !members[i]->cfg.optimize; }),
-                             (int)std::count_if(order.begin(), order.end(), [&](int i) { return members[i]->cfg.optimize != 0; })};
-      sffk::RrtSeqArgs* ha = args.h.as<sffk::RrtSeqArgs>();
-      size_t lds[2] = {0, 0};
-      for (size_t s = 0; s < order.size(); ++s) {   // (every member's drawn words reach its ring, whatever happens to another one:
-        cur = order[s];                             // a generator ahead of its ring would be an inconsistent session)
-        try {
-          if (!words[cur].empty()) members[cur]->batch_ring_append(words[cur].data(), words[cur].size());
-        } catch (...) { fail(cur); }
-      }
-      if (err) break;
-      for (size_t s = 0; s < order.size(); ++s) {
-        cur = order[s];
-        Rrt& r = *members[cur];
-        ha[s] = r.batch_prepare(iters_now[cur]);
-        const int kind = r.cfg.optimize ? 1 : 0;
-        lds[kind] = std::max(lds[kind], sffk::collide_lds_bytes(ha[s].rob.n_tri, 1));
-      }
-      // ---- 2. + 3. per kind: arguments up, one launch, the status blocks back - on the stream of the kind's first member
-      bool launched[2] = {false, false};
-      try {
-        for (int kind = 0; kind < 2; ++kind) {
-          if (!n_kind[kind]) continue;
-          const size_t first = kind ? (size_t)n_kind[0] : 0;
-          cur = order[first];
-          hipStream_t s = members[cur]->ctx->stream;
-          for (size_t j = first; j < first + (size_t)n_kind[kind]; ++j) {
-            Rrt::BatchDev& d = members[order[j]]->bd;
-            if (d.ring_pending) {
-              HIPCHK(hipStreamWaitEvent(s, d.ev_ring, 0));
-              d.ring_pending = false;
-            }
-          }
-          HIPCHK(hipMemcpyAsync(args.d.as<sffk::RrtSeqArgs>() + first, ha + first, (size_t)n_kind[kind] * sizeof(sffk::RrtSeqArgs),
-                                hipMemcpyHostToDevice, s));
-          HIPCHK(sffk::launch_rrt_seq_batch(s, args.d.as<sffk::RrtSeqArgs>() + first, n_kind[kind], kind != 0, lds[kind]));
-          launched[kind] = true;
-          for (size_t j = first; j < first + (size_t)n_kind[kind]; ++j) {
-            Rrt::BatchDev& d = members[order[j]]->bd;
-            HIPCHK(hipMemcpyAsync(d.h_ctrl.as<sffk::RrtCtrl>(), d.ctrl.p, sizeof(sffk::RrtCtrl), hipMemcpyDeviceToHost, s));
-          }
-        }
-      } catch (...) { fail(cur); }
-      for (int kind = 0; kind < 2; ++kind) {
-        if (!launched[kind]) continue;
-        cur = order[kind ? (size_t)n_kind[0] : 0];
-        try { HIPCHK(hipStreamSynchronize(members[cur]->ctx->stream)); } catch (...) { fail(cur); launched[kind] = false; }
-      }
-      // ---- 4. every member that ran is taken in, whatever happens to another one
-      for (size_t s = 0; s < order.size(); ++s) {
-        cur = order[s];
-        Rrt& r = *members[cur];
-        if (!launched[r.cfg.optimize ? 1 : 0]) continue;
-        try { r.batch_take_in(); } catch (...) { fail(cur); }
-      }
-      if (err) break;
-    }
-  } catch (...) { fail(cur); }
-  const double wall = ms_since(t0);
-  for (int i = 0; i < n; ++i) members[i]->st.total_ms += wall;
-  if (err) std::rethrow_exception(err);
+  RrtFamily fam{members, n, max_iterations, std::vector<int>((size_t)n)};
+  run_lockstep(fam, n, failed);
 }
 
 }  // namespace sff

@@ -219,6 +219,36 @@ def test_batch_refusals_leave_a_bystander_alone(S, pool):
     close_all([by, b])
 
 
+def test_batch_error_names_the_member_it_came_from(S, pool):
+    """a host-side refusal inside the lock step (Rrt::batch_upload: the context's store is another session's) carries the
+    index of the member it came from, wherever that member stands, and leaves the other member as it was"""
+    ro, by = member(S, pool[0], name="dense3d", seed=100, iters=1500)
+    ro.run()
+    by.run(60)
+    keys = ("iterations", "n_nodes", "collide_calls", "path_free_calls", "nn_queries", "rng_draws", "batch_launches", "waves")
+
+    def state():
+        n = by.nodes()
+        return tuple(by.stats()[k] for k in keys), n["pos"].tobytes(), n["parent"].tobytes(), n["cost"].tobytes()
+
+    st0 = state()
+    _, a = member(S, pool[1], name="dense3d", seed=101, iters=1500, run_oracle=False)
+    a.run(60)
+    assert a.stats()["n_nodes"] > 1                                        # (more nodes than its roots)
+    _, b = member(S, pool[1], name="dense3d", seed=102, iters=1500, run_oracle=False)      # (the same context: it took a's store)
+    for members, idx in (([by, a], 1), ([a, by], 0)):
+        with pytest.raises(S.SffGpuError) as e:
+            S.run_rrt_batch(members)
+        print(e.value)
+        assert "member %d" % idx in str(e.value) and "node store is not this session's" in str(e.value), str(e.value)
+    assert state() == st0
+    a.close()
+    S.run_rrt_batch([by, b])
+    assert by.stats()["batch_launches"] >= 1
+    assert_same_session(ro, by)
+    close_all([by, b])
+
+
 def test_batch_equals_the_sessions_run_alone(S, pool):
     """the three paths of this library on the same eight jobs: k_rrt_seq_batch, the one-by-one host loop, speculative waves"""
     keys = ("iterations", "solved", "n_nodes", "n_live_trees", "merges", "n_links", "collide_calls", "path_free_calls",
