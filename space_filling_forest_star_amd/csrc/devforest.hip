@@ -99,7 +99,7 @@ __global__ __launch_bounds__(256) void k_wave_begin(DevForestView f) {
   }
   if (c->in_wave) {   // resuming inside a wave (after the host handled a fault): the active list is in place
     // (the slots' sorted positions are not: the query kernel walks the sample indices for the rest of this wave)
-    if (blockIdx.x == 0 && threadIdx.x == 0) { c->compact_from = 0; c->app_n = 0; c->ord_valid = 0; round_begin_scalars(f, c); }
+    if (blockIdx.x == 0 && threadIdx.x == 0) { c->compact_from = 0; c->app_n = 0; c->ord_valid = 0; c->act_identity = 0; round_begin_scalars(f, c); }
     return;
   }
   // priority-frontier mode: the slots take their nodes from the trees' heaps (k_prio_begin, launched behind this kernel)
@@ -195,6 +195,7 @@ __global__ __launch_bounds__(256) void k_wave_begin(DevForestView f) {
   c->use_closed = use_closed ? 1 : 0;
   c->round = 0;
   c->in_wave = 1;
+  c->act_identity = 1;          // (act[sl] = sl above)
   c->waves += 1;
   c->prio_wave = 0;
   c->prio_n0 = c->n_nodes;
@@ -755,8 +756,8 @@ __global__ __launch_bounds__(1024) void k_commit(ResolveArgs A, int n_bound) {
 // (src/forest.h:353-367).  Runs although the NEXT round may already be halted: this commit is final.
 // One slot's share of the append.  Returns the slot's index in the NEXT round's active list (-1: none - accepted, or
 // nothing was committed) and the slot itself.
-// part: 0 = everything, 1 = only the accepted sample's node, 2 = only the next round's list (+ the claims of a wave that
-// is over) - k_append_sample runs the two parts in different workgroups.
+// part: 0 = everything, 1 = only the accepted sample's node (k_append_sample: the next round's list and the claims of a
+// wave that is over are written by its sampling workgroups, append_list_one).
 __device__ __forceinline__ void append_ord_store(const ResolveArgs& A, int ord_at, int next) {
   if (ord_at >= 0) (A.f.ctrl->app_act_sel ? A.f.ord.lst[0] : A.f.ord.lst[1])[ord_at] = next;
 }
@@ -812,7 +813,7 @@ __device__ __forceinline__ int append_one(const ResolveArgs& A, int i, int& slot
     if (wave_over) claim(i - rank, slot_out);
     return i - rank;
   }
-  if (A.star || part == 2) return -1;   // SFF*: k_star_apply has made the accepted samples nodes
+  if (A.star) return -1;   // SFF*: k_star_apply has made the accepted samples nodes
   const int N0 = c->app_N0, fn0 = c->app_fn0;
   int32_t* const frontier = frontier_now(f);
   const int id = N0 + rank;
@@ -916,6 +917,51 @@ __global__ __launch_bounds__(256) void k_append(ResolveArgs A, int append_blocks
   const int next = append_one(A, blockIdx.x * 256 + threadIdx.x, slot, ord_at);
   append_ord_store(A, ord_at, next);
 }
+// The sampling workgroups' share of the commit: the next round's active list (+ the claims of a wave that is over), and
+// which sample of the next round - if any - thread i draws, from which node.  Everything the thread index addresses is
+// asked for in ONE batch before anything is looked at: the control-block fields, the accepted word and its prefix, BOTH
+// active lists (the current one is selected afterwards) and the committed round's parent entry - a slot expands the same
+// node in every round of a wave, so the node of the next sample is A.parent[i], not slot_node[act_old[i]] two levels on;
+// the slot itself is only stored (the next list) and, when the wave is over, claimed.  A.parent is the committed round's
+// list, the sampler's parent_out the other one of the two: reading the one while the other is written is no race.
+// bound = the launch bound (the lists hold that many entries whatever the round's size): clamped indices keep the
+// threads behind it harmless.  Returns the sample's index in the next round (-1: none); K = the sampler's control fields.
+__device__ __forceinline__ int append_list_one(const ResolveArgs& A, int i, int bound, int& par, SampleCtl& K) {
+  const DevForestView& f = A.f;
+  const DevCtrl* c = f.ctrl;   // (the sampler's control block too)
+  const int ic = i < bound ? i : bound - 1;
+  unsigned long long w = f.w_acc[ic >> 6];
+  int pref = f.acc_pref[ic >> 6];
+  int s0 = f.act_slot[ic], s1 = f.act_slot2[ic];
+  int ex = A.parent[ic];
+  K = sample_ctl(c);
+  int n = c->app_n, act_cnt = c->app_act_cnt, app_sel = c->app_act_sel, new_cnt = c->act_cnt;
+  int in_wave = c->in_wave, use_closed = c->use_closed;
+  join_ctl_v(K);
+  join_v(n, act_cnt, app_sel, new_cnt, in_wave, use_closed, w, pref, s0, s1, ex);
+  const bool wave_over = K.n == 0 && !K.halt && in_wave && !use_closed;
+  par = 0;
+  if (n <= 0) return -1;
+  const int slot = app_sel ? s1 : s0;
+  int32_t* act_new = app_sel ? f.act_slot : f.act_slot2;
+  if (wave_over && i == 0) f.ctrl->claims_done = 1;
+  if (i >= n) {
+    // the slots the iteration cap kept out of the committed round stay on the list, behind the still-failing ones
+    // (the cap has been reached: they never draw again; they drew nothing in the committed round either - no parent entry)
+    if (i < act_cnt) {
+      const int e = (new_cnt - (act_cnt - n)) + (i - n);
+      act_new[e] = slot;
+      if (wave_over) { const int nd = f.slot_node[slot]; atomicMin(&f.claim[nd], e); f.ulist[e] = nd; }
+    }
+    return -1;
+  }
+  if ((w >> (i & 63)) & 1ULL) return -1;   // accepted: the node-creating workgroups (SFF*: k_star_apply) have it
+  const int next = i - (pref + __popcll(w & ((1ULL << (i & 63)) - 1ULL)));   // (the accepted samples before it leave the list)
+  par = ex;
+  act_new[next] = slot;                  // not accepted: the slot tries again
+  if (wave_over) { atomicMin(&f.claim[ex], next); f.ulist[next] = ex; }
+  return next;
+}
 // k_append + the NEXT round's k_sample_steer in one launch: a slot that was not accepted draws its next sample right
 // away (its place in the next round's list is its old place minus the accepted samples before it; the round's size,
 // word base and epoch are in the control block since k_commit).  The sample reads what the append of this very launch
@@ -929,11 +975,18 @@ __global__ __launch_bounds__(256) void k_append_sample(ResolveArgs A, SampleLaun
   const int nb = append_blocks;
   const bool sampler = (int)blockIdx.x >= nb;
   const int tid = ((int)blockIdx.x - (sampler ? nb : 0)) * 256 + threadIdx.x;
-  int slot, ord_at;
-  if (!sampler) { (void)append_one(A, tid, slot, ord_at, 1); return; }
-  const int next = append_one(A, tid, slot, ord_at, 2);
-  sample_steer_one(tid, next, slot < 0 ? -2 : slot, P);   // (-1 is k_sample_steer's "look the slot up")
-  append_ord_store(A, ord_at, next);
+  if (!sampler) {
+    int slot, ord_at;
+    (void)append_one(A, tid, slot, ord_at, 1);
+    return;
+  }
+  int par;
+  SampleCtl K;
+  const int next = append_list_one(A, tid, P.n, par, K);
+  if (K.halt) return;
+  const bool valid = next >= 0 && next < K.n;
+  const SampleIn S = sample_fetch(valid ? next : 0, valid ? par : 0, K, P);
+  sample_finish(tid, valid, next, par, S, -1, K, P);
 }
 
 // the control block at the end of a wave: closed list / frontier sizes, termination (src/forest.h:184-201); one thread

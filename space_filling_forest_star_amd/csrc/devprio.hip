@@ -165,6 +165,7 @@ __global__ __launch_bounds__(64) void k_prio_begin(DevForestView f) {
     c->use_closed = 0;
     c->round = 0;
     c->in_wave = 1;
+    c->act_identity = 1;
     c->waves += 1;
     c->prio_wave = 1;
     c->prio_gen = (int32_t)c->waves;
@@ -292,6 +293,7 @@ __global__ __launch_bounds__(1024) void k_prio_plan(DevForestView f) {
   c->use_closed = 0;
   c->round = 0;
   c->in_wave = 1;
+  c->act_identity = 1;
   c->waves += 1;
   c->prio_wave = 1;
   c->prio_gen = (int32_t)c->waves;

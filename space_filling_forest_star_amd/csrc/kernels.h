@@ -198,7 +198,10 @@ struct DevCtrl {
   int32_t app_nb0;
   // status blocks published so far (DevForestView::host_status): the wave's last kernel writes the control block straight
   // into a ring of pinned host memory, numbered by this counter - no copy launch behind every wave
-  int32_t status_seq, status_pad;
+  int32_t status_seq;
+  // 1 = the wave's active list is still the identity (slot s holds sample s) while round == 1: written by the kernels
+  // that begin a fresh wave, cleared when a wave is resumed - k_sample_steer then asks for slot_node[thread] at once
+  int32_t act_identity;
   // waves of one slot, speculated (k_spec_waves): steps (publish -> evaluate -> commit), attempts the workers evaluated,
   // attempts that were committed; stalled = a worker's record did not arrive in time (the host goes back to k_seq_waves)
   unsigned long long spec_steps, spec_evaluated, spec_committed;

@@ -35,7 +35,7 @@ using namespace sffg;
 // ------------------------------------------------------------------ sample + steer
 __global__ __launch_bounds__(256) void k_sample_steer(SampleLaunch P) {
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
-  sample_steer_one(i, i, -1, P);
+  sample_steer_one(i, P);
 }
 
 // ------------------------------------------------------------------ neighbour sweep

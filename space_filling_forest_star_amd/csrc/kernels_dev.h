@@ -190,15 +190,82 @@ __device__ __forceinline__ void star_cells_mates(const GridView& tg, int m, int 
 
 
 // ---- sample + steer of one slot (k_sample_steer; the device engine's k_append_sample runs it for the NEXT round right
-// behind the append).  tid = the thread's index in the launch (per-round housekeeping), i = the sample it draws (< 0:
-// none), slot >= 0: the sample's slot (k_append_sample knows it; otherwise it is read from the active list).
-__device__ __forceinline__ void sample_steer_one(int tid, int i, int slot, const SampleLaunch& P) {
+// behind the append).  The kernels are latency bound (one thread per sample, a few thousand samples): what they cost is
+// the number of DEPENDENT memory levels, so the sample's inputs are fetched in two batches whose loads leave together -
+//   1. what the thread index alone addresses: the control-block fields (sample_ctl), the caller's own lists;
+//   2. what the expanded node and the sample's index address (sample_fetch): position / flag / tree of the node, the
+//      engine words, the host's trig values in libm parity mode -
+// and every store comes behind them (sample_finish): a store may alias a later load, which then cannot leave early.
+// Out-of-range threads fetch with harmless indices (node 0, sample 0) instead of branching around the loads.
+struct SampleCtl {
+  int32_t n, halt, act_sel, round, ord_valid, n_slots, act_identity;
+  unsigned long long words_base;
+};
+__device__ __forceinline__ SampleCtl sample_ctl(const DevCtrl* c) {
+  SampleCtl K;
+  K.n = c->n_act; K.halt = c->halt; K.act_sel = c->act_sel; K.round = c->round; K.ord_valid = c->ord_valid;
+  K.n_slots = c->n_slots; K.act_identity = c->act_identity; K.words_base = c->words_base;
+  return K;
+}
+// The end of a batch of loads.  The compiler sinks a load into the branch that uses its value and waits for a value
+// where it is first looked at - either way the loads of a batch would leave one after the other again.  These empty
+// statements "use" the values: every load written above them has been issued when the first one is reached (they
+// count as memory accesses, so no load moves across), and nothing behind them moves up.  join_u: values that came
+// through the scalar cache (control-block fields of a kernel that writes none: k_sample_steer; on a value the compiler
+// holds in a vector register the "s" constraint does not compile), join_v: values in vector registers.  Call ONE of
+// them per batch with every value the batch loads.  Nothing in the suite can see a batch fall apart again: after a
+// compiler upgrade look at the kernels' -S output (the batch's loads in front of the first s_waitcnt on any of
+// them) and at profiles/kernel_regs.sh.
+template <class T> __device__ __forceinline__ void join_one_u(T& x) { asm volatile("" : "+s"(x) : : "memory"); }
+template <class T> __device__ __forceinline__ void join_one_v(T& x) { asm volatile("" : "+v"(x) : : "memory"); }
+template <class... T> __device__ __forceinline__ void join_u(T&... x) { (join_one_u(x), ...); }
+template <class... T> __device__ __forceinline__ void join_v(T&... x) { (join_one_v(x), ...); }
+__device__ __forceinline__ void join_ctl_u(SampleCtl& K) {
+  join_u(K.n, K.halt, K.act_sel, K.round, K.ord_valid, K.n_slots, K.act_identity, K.words_base);
+}
+__device__ __forceinline__ void join_ctl_v(SampleCtl& K) {
+  join_v(K.n, K.halt, K.act_sel, K.round, K.ord_valid, K.n_slots, K.act_identity, K.words_base);
+}
+struct SampleIn {
+  double c[6];          // the expanded node's position (or the caller's centre)
+  uint64_t w[6];        // the sample's engine words
+  sffg::SampleTrig trig;
+  int32_t tree;         // the node's tree
+  uint8_t force;        // its ForceChildren flag
+};
+// the second batch.  i and par are in range (the caller replaces those of a thread without a sample by 0)
+__device__ __forceinline__ SampleIn sample_fetch(int i, int par, const SampleCtl& K, const SampleLaunch& P) {
+  const DevRound& dv = P.dv;
+  SampleIn S{};
+  const double* src = P.center_in ? P.center_in + 6 * (size_t)i : P.node_pos + 6 * (size_t)par;
+  for (int k = 0; k < 6; ++k) S.c[k] = src[k];
+  if (P.tmp.cnt) S.tree = P.tmp.st.tree[par];
+  if (dv.ctrl) {   // the sample's words sit in the engine-word ring, in the reference's draw order
+    S.force = dv.nflag[par] & 1;
+    const unsigned long long base = K.words_base + (unsigned long long)dv.words_per * (unsigned long long)i;
+    for (int k = 0; k < 6; ++k) S.w[k] = k < dv.words_per ? dv.ring[(base + k) & dv.ring_mask] : 0ULL;
+    if (dv.trig) {   // libm parity mode: the transcendental values of these words, evaluated by the host's C library
+      const double* t0 = dv.trig + 3 * (size_t)(base & dv.ring_mask);
+      S.trig.c_phi = t0[0]; S.trig.s_phi = t0[1];
+      if (dv.words_per == 6) {
+        const double* t1 = dv.trig + 3 * (size_t)((base + 1) & dv.ring_mask);
+        const double* t3 = dv.trig + 3 * (size_t)((base + 3) & dv.ring_mask);
+        S.trig.c_theta = t1[0]; S.trig.s_theta = t1[1];
+        S.trig.acos_u = t3[2];
+      }
+    }
+  } else {
+    for (int k = 0; k < 6; ++k) S.w[k] = P.words[6 * (size_t)i + k];
+  }
+  return S;
+}
+// everything that stores.  tid = the thread's index in the launch (per-round housekeeping), valid: the thread draws
+// sample i from node par with the inputs S; ord_pos >= 0: the wave's first sampling launch - slot tid takes this
+// position in the wave's spatial order.
+__device__ __forceinline__ void sample_finish(int tid, bool valid, int i, int par, const SampleIn& S, int ord_pos,
+                                              const SampleCtl& K, const SampleLaunch& P) {
   using namespace sffg;
-  const uint64_t* __restrict__ words = P.words;
-  const int32_t* __restrict__ parent = P.parent;
-  const double* __restrict__ node_pos = P.node_pos;
-  const double* __restrict__ center_in = P.center_in;
-  int n = P.n;
+  const int n = K.n;
   const double dist = P.dist;
   const int dim = P.dim;
   const SampleParams& prm = P.prm;
@@ -209,9 +276,7 @@ __device__ __forceinline__ void sample_steer_one(int tid, int i, int slot, const
   const int32_t q_max_base = P.q_max_base;
   const RoundTemps& tmp = P.tmp;
   const DevRound& dv = P.dv;
-  if (dv.ctrl) {   // device-resident forest: the round's size lives in HBM
-    if (dv.ctrl->halt) return;
-    n = dv.ctrl->n_act;
+  if (dv.ctrl) {
     if (tid == 0 && dv.qclk) { dv.qclk[0] = ~0ULL; dv.qclk[1] = 0ULL; }
     if (dv.qclk_sh && tid < 128) dv.qclk_sh[(tid >> 1) * 16 + (tid & 1)] = (tid & 1) ? ~0ULL : 0ULL;
   }
@@ -230,48 +295,24 @@ __device__ __forceinline__ void sample_steer_one(int tid, int i, int slot, const
       tmp.st.yaw[o] = nanv; tmp.st.pitch[o] = nanv; tmp.st.roll[o] = nanv;
     }
   }
-  // the wave's first sampling launch (sample index == slot): every slot gets its position in the wave's spatial order
-  if (dv.ctrl && dv.ord.hist && slot == -1 && dv.ctrl->ord_valid && dv.ctrl->round == 1 && tid < dv.ctrl->n_slots) {
-    const int pos = dv.ord.start[dv.ord.slot_key[tid]] + dv.ord.slot_rank[tid];
-    const int sel = dv.ctrl->act_sel, n_slots = dv.ctrl->n_slots;
+  if (ord_pos >= 0) {
+    const int sel = K.act_sel, n_slots = K.n_slots, pos = ord_pos;
     dv.ord.slot_pos[tid] = pos;
     (sel ? dv.ord.lst[1] : dv.ord.lst[0])[pos] = tid < n ? tid : -1;      // (this round: every position holds its slot's sample)
     if ((pos & 63) == 0) (sel ? dv.ord.cnt[1] : dv.ord.cnt[0])[(pos >> 6) * SFFK_ORD_CNT_STRIDE] = n_slots - pos < 64 ? n_slots - pos : 64;
   }
-  if (i < 0 || i >= n) return;
+  if (!valid) return;
   double c[6], o[6];
-  int par = 0;
-  if (dv.ctrl) {
-    par = dv.slot_node[slot >= 0 ? slot : (dv.ctrl->act_sel ? dv.act_slot2 : dv.act_slot)[i]];
-    dv.parent_out[i] = par;
-    dv.force_out[i] = dv.nflag[par] & 1;
-  } else if (!center_in) {
-    par = parent[i];
-  }
-  const double* src = center_in ? center_in + 6 * (size_t)i : node_pos + 6 * (size_t)par;
-  for (int k = 0; k < 6; ++k) c[k] = src[k];
-  if (tmp.center_out) for (int k = 0; k < 6; ++k) tmp.center_out[6 * (size_t)i + k] = c[k];
   uint64_t w[6];
-  SampleTrig host_trig{};
-  if (dv.ctrl) {   // the sample's words sit in the engine-word ring, in the reference's draw order
-    const unsigned long long base = dv.ctrl->words_base + (unsigned long long)dv.words_per * (unsigned long long)i;
-    for (int k = 0; k < 6; ++k) w[k] = k < dv.words_per ? dv.ring[(base + k) & dv.ring_mask] : 0ULL;
-    if (dv.trig) {   // libm parity mode: the transcendental values of these words, evaluated by the host's C library
-      const double* t0 = dv.trig + 3 * (size_t)(base & dv.ring_mask);
-      host_trig.c_phi = t0[0]; host_trig.s_phi = t0[1];
-      if (dv.words_per == 6) {
-        const double* t1 = dv.trig + 3 * (size_t)((base + 1) & dv.ring_mask);
-        const double* t3 = dv.trig + 3 * (size_t)((base + 3) & dv.ring_mask);
-        host_trig.c_theta = t1[0]; host_trig.s_theta = t1[1];
-        host_trig.acos_u = t3[2];
-      }
-    }
-  } else {
-    for (int k = 0; k < 6; ++k) w[k] = words[6 * (size_t)i + k];
+  for (int k = 0; k < 6; ++k) { c[k] = S.c[k]; w[k] = S.w[k]; }
+  if (dv.ctrl) {
+    dv.parent_out[i] = par;
+    dv.force_out[i] = S.force;
   }
+  if (tmp.center_out) for (int k = 0; k < 6; ++k) tmp.center_out[6 * (size_t)i + k] = c[k];
   bool ok;
   if (dv.ctrl && dv.trig) {
-    ok = sample_point_with(w, c, dist, dim, prm.limits, o, host_trig);
+    ok = sample_point_with(w, c, dist, dim, prm.limits, o, S.trig);
   } else if (tmp.preset) {
     for (int k = 0; k < 6; ++k) o[k] = tmp.preset[6 * (size_t)i + k];
     ok = in_limits(o, prm.limits);
@@ -280,6 +321,7 @@ __device__ __forceinline__ void sample_steer_one(int tid, int i, int slot, const
   }
   for (int k = 0; k < 6; ++k) out6[6 * (size_t)i + k] = o[k];
   in_lim[i] = ok ? 1 : 0;
+  const int tr = S.tree;
   if (tmp.cnt) {
     // the sample becomes temporary store entry base + i (NaN floats when out of limits, so that no query
     // can match it), with the tree of the node it was expanded from
@@ -292,7 +334,6 @@ __device__ __forceinline__ void sample_steer_one(int tid, int i, int slot, const
     tmp.st.pitch[t] = ok ? (float)o[4] : nanv;
     tmp.st.roll[t] = ok ? (float)o[5] : nanv;
     for (int k = 0; k < 6; ++k) tmp.st.pos[6 * t + k] = o[k];
-    const int tr = tmp.st.tree[par];
     tmp.st.tree[t] = tr;
     if (ok && tmp.tg.cnt) {   // and into the round's own grid, where the later samples of the round look for it
       GridItem it;
@@ -323,7 +364,7 @@ __device__ __forceinline__ void sample_steer_one(int tid, int i, int slot, const
         QRec r;
         r.q[0] = q.x; r.q[1] = q.y; r.q[2] = q.z; r.q[3] = q.yaw; r.q[4] = q.pitch; r.q[5] = q.roll;
         r.r2f = q.r2f; r.max_id = q.max_id; r.q_tree = q.tree;
-        r.mine = tmp.cnt ? tmp.st.tree[par] : 0;
+        r.mine = tr;
         r.evaluate = q.active;
         // the cells the query ball's box touches (the round's own grid has the node grid's cells)
         const GridView& g = tmp.tg;
@@ -347,6 +388,41 @@ __device__ __forceinline__ void sample_steer_one(int tid, int i, int slot, const
       }
     }
   }
+}
+
+// k_sample_steer: thread tid draws sample tid; its node comes from the caller's parent list (host replay), from the
+// caller's centres, or - device engine - from its slot.  In the first round of a fresh wave the active list is the
+// identity (DevCtrl::act_identity), so the slot's node is asked for in the first batch; otherwise (a resumed wave,
+// SFFGPU_NO_FUSED_SAMPLE's later rounds) the slot is looked up in the active list first: one level more.
+__device__ __forceinline__ void sample_steer_one(int tid, const SampleLaunch& P) {
+  const DevRound& dv = P.dv;
+  const int tc = tid < P.n ? tid : P.n - 1;   // (P.n = the launch bound: every per-sample / per-slot array holds that many)
+  SampleCtl K{};
+  K.n = P.n;
+  int par = 0, a0 = 0, a1 = 0, key = 0, rnk = 0;
+  if (dv.ctrl) {
+    // (spatial order off: any int per slot will do - no branch around two of the batch's loads)
+    const int32_t* kp = dv.ord.hist ? dv.ord.slot_key : dv.act_slot;
+    const int32_t* rp = dv.ord.hist ? dv.ord.slot_rank : dv.act_slot;
+    a0 = dv.act_slot[tc]; a1 = dv.act_slot2[tc];
+    par = dv.slot_node[tc];
+    key = kp[tc]; rnk = rp[tc];
+    K = sample_ctl(dv.ctrl);
+    join_ctl_u(K);
+    join_v(a0, a1, par, key, rnk);
+  } else if (!P.center_in) {
+    par = P.parent[tc];
+  }
+  if (K.halt) return;
+  const bool valid = tid < K.n;
+  // (not the identity: the first batch's slot_node entry was some other slot's - one level more)
+  if (dv.ctrl && !(K.act_identity && K.round == 1)) par = dv.slot_node[valid ? (K.act_sel ? a1 : a0) : 0];
+  if (!valid) par = 0;
+  // the wave's first sampling launch (sample index == slot): every slot gets its position in the wave's spatial order
+  const bool ord_now = dv.ctrl && dv.ord.hist && K.ord_valid && K.round == 1 && tid < K.n_slots;
+  const SampleIn S = sample_fetch(valid ? tid : 0, par, K, P);
+  const int start = dv.ctrl && dv.ord.hist ? dv.ord.start[ord_now ? key : 0] : 0;   // (with the second batch)
+  sample_finish(tid, valid, tid, par, S, ord_now ? start + rnk : -1, K, P);
 }
 
 }  // namespace sffk
