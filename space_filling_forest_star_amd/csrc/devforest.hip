@@ -35,18 +35,6 @@ using namespace sffg;
 
 __device__ __forceinline__ int record_words_dev(int nbcap) { return 6 + 4 * nbcap; }
 
-// libstdc++ uniform_int_distribution<int>(0, range - 1) on one 64-bit engine word (Lemire's multiply-shift):
-// returns the draw, or -1 when the word falls into the rejection zone (the reference then draws again)
-__device__ __forceinline__ int lemire_pick(unsigned long long word, unsigned long long range) {
-  const unsigned long long lo = word * range;
-  const unsigned long long hi = __umul64hi(word, range);
-  if (lo < range) {
-    const unsigned long long thr = (0ULL - range) % range;
-    if (lo < thr) return -1;
-  }
-  return (int)hi;
-}
-
 __device__ __forceinline__ int32_t* frontier_now(const DevForestView& f) { return f.ctrl->front_sel ? f.frontier2 : f.frontier; }
 __device__ __forceinline__ int32_t* act_now(const DevForestView& f) { return f.ctrl->act_sel ? f.act_slot2 : f.act_slot; }
 

@@ -26,16 +26,6 @@ namespace sffk {
 
 using namespace sffg;
 
-__device__ __forceinline__ int prio_lemire(unsigned long long word, unsigned long long range) {   // (devforest.hip: lemire_pick)
-  const unsigned long long lo = word * range;
-  const unsigned long long hi = __umul64hi(word, range);
-  if (lo < range) {
-    const unsigned long long thr = (0ULL - range) % range;
-    if (lo < thr) return -1;
-  }
-  return (int)hi;
-}
-
 #ifdef SFFK_PRIO_DEBUG
 __device__ unsigned long long g_prio_dbg[16];
 #endif
@@ -121,7 +111,7 @@ __global__ __launch_bounds__(64) void k_prio_begin(DevForestView f) {
   };
   auto draw_int = [&](int range) -> int {        // RandGen::randomIntMinMax(0, range - 1)
     int v;
-    do { v = prio_lemire(next_word(), (unsigned long long)range); } while (v < 0);
+    do { v = lemire_pick(next_word(), (unsigned long long)range); } while (v < 0);
     return v;
   };
   int32_t* act = prio_act_now(f);
@@ -265,12 +255,12 @@ __global__ __launch_bounds__(1024) void k_prio_plan(DevForestView f) {
     const unsigned long long w1 = f.ring[(cur + (unsigned long long)p + 1ULL) & f.ring_mask];
     const int nx = hop(p);
     bool bad = false;
-    int t = prio_lemire(w0, (unsigned long long)T), hp = 0, idx = -1;
+    int t = lemire_pick(w0, (unsigned long long)T), hp = 0, idx = -1;
     unsigned long long w3 = 0ULL;
     if (t < 0) { bad = true; t = 0; }
     else {
       const int b0 = P.base[t], nh = P.base[t + 1] - b0;
-      hp = nh > 0 ? prio_lemire(w1, (unsigned long long)nh) : -1;
+      hp = nh > 0 ? lemire_pick(w1, (unsigned long long)nh) : -1;
       if (hp < 0) { bad = true; hp = 0; }
       else {
         atomicAdd(&s_cnt[b0 + hp], 1);
@@ -360,7 +350,7 @@ __global__ __launch_bounds__(256) void k_prio_pops(DevForestView f) {
       for (int e = 0; e < total; ++e) {
         int id = uni_i32(s_idx[e]);
         if (id == -2) {   // (planned in parallel: the random entry's index is drawn here, with the heap's size at this turn)
-          id = prio_lemire(uni_u64(s_word[e]), (unsigned long long)hr.n);
+          id = lemire_pick(uni_u64(s_word[e]), (unsigned long long)hr.n);
           if (id < 0) { if (lane == 0) f.ctrl->fault = SFFK_FAULT_PRIO_REDRAW; id = 0; }
         }
         const int node = id < 0 ? heap_pop(hr) : heap_pop_at(hr, id);

@@ -4042,29 +4042,7 @@ __global__ __launch_bounds__(256) void k_settle(SettleArgs A) {
 }
 
 // ------------------------------------------------------------------ waves of one slot: the reference's loop, one wavefront
-// Loads of forest state this launch may itself have written go past the vector L1 (agent-scope relaxed atomic loads =
-// `sc1` loads served by the L2 the one workgroup's stores write through to); the environment, the robot and the engine
-// words are immutable while it runs.
-__device__ __forceinline__ int sq_i32(const int32_t* p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
-__device__ __forceinline__ unsigned long long sq_u64(const unsigned long long* p) {
-  return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
-__device__ __forceinline__ double sq_f64(const double* p) {
-  return __longlong_as_double((long long)__hip_atomic_load(reinterpret_cast<const unsigned long long*>(p), __ATOMIC_RELAXED,
-                                                            __HIP_MEMORY_SCOPE_AGENT));
-}
-__device__ __forceinline__ int sq_u8(const uint8_t* p) { return (int)__hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
-__device__ __forceinline__ void sq_drain() { asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); }
-
-__device__ __forceinline__ int sq_lemire(unsigned long long word, unsigned long long range) {   // (devforest.hip: lemire_pick)
-  const unsigned long long lo = word * range;
-  const unsigned long long hi = __umul64hi(word, range);
-  if (lo < range) {
-    const unsigned long long thr = (0ULL - range) % range;
-    if (lo < thr) return -1;
-  }
-  return (int)hi;
-}
+// (the sq_* loads that go past the vector L1, sq_drain and lemire_pick: kernels_dev.h)
 
 // isPathFree's common case INLINE: every sample of the edge lies in a cell the clearance bits (edge plane) call clear - the
 // same placement arithmetic as sq_path_free's first phase, so the same bits are asked; edges of up to 512 samples.  True =
@@ -4459,6 +4437,13 @@ __device__ __attribute__((noinline)) void sq_knn(const GridView& g, const double
   if (dbg && lane == 0) { atomicAdd(dbg, d_sh); atomicAdd(dbg + 1, d_cg); atomicAdd(dbg + 2, d_ob); atomicAdd(dbg + 3, d_in); atomicAdd(dbg + 4, 1ULL); atomicAdd(dbg + 5, (unsigned long long)no); }
 }
 
+// a kernel that asks for more dynamic LDS than `threshold` bytes has to be told so before its launch
+template <class K>
+static hipError_t set_dyn_lds(K kernel, size_t lds, size_t threshold) {
+  if (lds <= threshold) return hipSuccess;
+  return hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+}
+
 // the loop itself is seq_waves_body.inc.  k_seq_waves includes it as text, on its by-value argument, which keeps this entry's
 // code as it was before the loop was shared; seq_waves_body is the same loop as a function of a reference (k_seq_waves_batch)
 template <bool OPT, bool PRIO>
@@ -4484,11 +4469,8 @@ __global__ __launch_bounds__(64) void k_seq_waves_batch(const SeqArgs* __restric
 
 template <bool OPT, bool PRIO>
 static hipError_t launch_seq_waves_batch_as(hipStream_t s, const SeqArgs* members_dev, int n, size_t lds) {
-  if (lds > 48 * 1024) {
-    const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(k_seq_waves_batch<OPT, PRIO>),
-                                             hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    if (e != hipSuccess) return e;
-  }
+  const hipError_t e = set_dyn_lds(k_seq_waves_batch<OPT, PRIO>, lds, 48 * 1024);
+  if (e != hipSuccess) return e;
   hipLaunchKernelGGL((k_seq_waves_batch<OPT, PRIO>), dim3(n), dim3(64), lds, s, members_dev, n);
   return hipGetLastError();
 }
@@ -4502,7 +4484,7 @@ hipError_t launch_seq_waves_batch(hipStream_t s, const SeqArgs* members_dev, int
 
 template <bool OPT, bool PRIO>
 static void launch_seq_waves_as(hipStream_t s, const SeqArgs& a, size_t lds) {
-  if (lds > 48 * 1024) (void)hipFuncSetAttribute(reinterpret_cast<const void*>(k_seq_waves<OPT, PRIO>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+  (void)set_dyn_lds(k_seq_waves<OPT, PRIO>, lds, 48 * 1024);
   hipLaunchKernelGGL((k_seq_waves<OPT, PRIO>), dim3(1), dim3(64), lds, s, a);
 }
 void launch_seq_waves(hipStream_t s, const SeqArgs& a) {
@@ -4513,15 +4495,7 @@ void launch_seq_waves(hipStream_t s, const SeqArgs& a) {
 }
 
 // ------------------------------------------------------------------ waves of one slot, SPECULATED (kernels.h: SpecArgs)
-// write-through stores: what the leader writes and a worker on another XCD reads in the same launch
-__device__ __forceinline__ void wt_i32(int32_t* p, int v) { __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
-__device__ __forceinline__ void wt_u64(unsigned long long* p, unsigned long long v) {
-  __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
-__device__ __forceinline__ void wt_f64(double* p, double v) {
-  wt_u64(reinterpret_cast<unsigned long long*>(p), (unsigned long long)__double_as_longlong(v));
-}
-__device__ __forceinline__ void wt_u8(uint8_t* p, uint8_t v) { __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
+// (wt_*, the write-through stores for what the leader writes and a worker on another XCD reads in the same launch: kernels_dev.h)
 __device__ __forceinline__ unsigned long long sp_gran(uint32_t tag, uint32_t v) { return ((unsigned long long)tag << 32) | (unsigned long long)v; }
 __device__ __forceinline__ uint32_t sp_lo(double v) { return (uint32_t)((unsigned long long)__double_as_longlong(v) & 0xffffffffULL); }
 __device__ __forceinline__ uint32_t sp_hi(double v) { return (uint32_t)((unsigned long long)__double_as_longlong(v) >> 32); }
@@ -4814,7 +4788,7 @@ __global__ __launch_bounds__(OPT ? 192 : 128) void k_spec_waves(SpecArgs S) {
         if (pool < 1) { terminated = 1; break; }
         unsigned long long cur2 = cursor, rdw = 0;
         int pick;
-        do { pick = sq_lemire(f.ring[cur2 & f.ring_mask], (unsigned long long)pool); ++cur2; if (pick < 0) ++rdw; } while (pick < 0);
+        do { pick = lemire_pick(f.ring[cur2 & f.ring_mask], (unsigned long long)pool); ++cur2; if (pick < 0) ++rdw; } while (pick < 0);
         const int idx = use_closed ? pick : er_map(pick);
         const bool own = !use_closed && idx >= fn_pc + (nn_base - nn_c);   // (a node of this step: no scenario models that)
         const unsigned long long* rec0 = S.rec + ((size_t)set * S.n_slots + (size_t)sc * TM) * SFFK_SPEC_REC;
@@ -5205,7 +5179,7 @@ __global__ __launch_bounds__(OPT ? 192 : 128) void k_spec_waves(SpecArgs S) {
       const int pool = ucl ? scn : sfn;
       if (pool < 1) { valid = false; break; }
       int pk;
-      do { pk = sq_lemire(f.ring[cur & f.ring_mask], (unsigned long long)pool); ++cur; } while (pk < 0);
+      do { pk = lemire_pick(f.ring[cur & f.ring_mask], (unsigned long long)pool); ++cur; } while (pk < 0);
       const int o = out_[l];
       if (o < TM) {                              // accepted at attempt o: one more node, at the frontier's end
         if (sit + o + 1 > f.max_iterations) { valid = false; break; }
@@ -5234,7 +5208,7 @@ __global__ __launch_bounds__(OPT ? 192 : 128) void k_spec_waves(SpecArgs S) {
       if (pool < 1) valid = false;
       else {
         int pk;
-        do { pk = sq_lemire(f.ring[cur & f.ring_mask], (unsigned long long)pool); ++cur; } while (pk < 0);
+        do { pk = lemire_pick(f.ring[cur & f.ring_mask], (unsigned long long)pool); ++cur; } while (pk < 0);
         if (ucl) { if (pk >= cn0) valid = false; else { pick_idx = pk; node = sq_i32(f.closed + pk); } }
         else if (pk >= fn0 - ne) valid = false;
         else {
@@ -5742,10 +5716,10 @@ void launch_spec_waves(hipStream_t s, const SpecArgs& a) {
   const size_t lds = collide_lds_bytes(a.q.rob.n_tri, 1);
   const unsigned grid = 1u + (unsigned)(a.n_sets * a.n_slots);
   if (a.q.optimize) {
-    if (lds > 32 * 1024) (void)hipFuncSetAttribute(reinterpret_cast<const void*>(k_spec_waves<true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    (void)set_dyn_lds(k_spec_waves<true>, lds, 32 * 1024);
     hipLaunchKernelGGL(k_spec_waves<true>, dim3(grid), dim3(192), lds, s, a);
   } else {
-    if (lds > 32 * 1024) (void)hipFuncSetAttribute(reinterpret_cast<const void*>(k_spec_waves<false>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    (void)set_dyn_lds(k_spec_waves<false>, lds, 32 * 1024);
     hipLaunchKernelGGL(k_spec_waves<false>, dim3(grid), dim3(128), lds, s, a);
   }
 }
@@ -5876,7 +5850,7 @@ void launch_collide_poses(hipStream_t s, const EnvView& env, const RobotView& ro
                           const int32_t* live_flags, uint8_t* hit, bool explicit_rt) {
   if (n <= 0) return;
   size_t lds = collide_lds_bytes(rob.n_tri, POSE_WAVES);
-  if (lds > 48 * 1024) (void)hipFuncSetAttribute(reinterpret_cast<const void*>(k_collide_poses), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+  (void)set_dyn_lds(k_collide_poses, lds, 48 * 1024);
   hipLaunchKernelGGL(k_collide_poses, dim3((n + POSE_WAVES - 1) / POSE_WAVES), dim3(64 * POSE_WAVES), lds, s, env,
                      rob, pos6, n, live_flags, hit, explicit_rt ? 1 : 0);
 }
@@ -5954,7 +5928,7 @@ void launch_collide_items(hipStream_t s, const sff::Knobs& kn, const EnvView& en
   // 26 908, chunks with 35-130 candidates; dense_3D's 1 832 give 2-8 per item); SFFGPU_SHARE=0 / 1 overrides
   const bool share = kn.share >= 0 ? kn.share != 0 : env.n_tri > 4096;
   auto kern = share ? k_collide_items<true> : k_collide_items<false>;
-  if (lds > 48 * 1024) (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+  (void)set_dyn_lds(kern, lds, 48 * 1024);
   // 2 workgroups of 4 waves per CU = what the exact kernel's register budget keeps resident (256 CUs)
   const int blocks = kn.seg_blocks ? kn.seg_blocks : 256 * CI_OCC;
   hipLaunchKernelGGL(kern, dim3(blocks), dim3(64 * SEG_WAVES), lds, s, env, rob, pos6, n_pose, live_flags, pose_hit,
@@ -5967,7 +5941,7 @@ void launch_collide_items(hipStream_t s, const sff::Knobs& kn, const EnvView& en
 void launch_star_exact(hipStream_t s, const EnvView& env, const RobotView& rob, const double* store_pos, const StarView& S,
                        int pass, int seg_blocks) {
   size_t lds = collide_lds_bytes(rob.n_tri, SEG_WAVES);
-  if (lds > 48 * 1024) (void)hipFuncSetAttribute(reinterpret_cast<const void*>(k_star_exact), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+  (void)set_dyn_lds(k_star_exact, lds, 48 * 1024);
   const int blocks = seg_blocks ? seg_blocks : 256 * CI_OCC;
   hipLaunchKernelGGL(k_star_exact, dim3(blocks), dim3(64 * SEG_WAVES), lds, s, env, rob, store_pos, S.ida, S.idb,
                      static_cast<const SurvivorItem*>(S.items), S.items_cap, S.sub + (size_t)pass * SFFK_SUBLISTS * SFFK_STAR_SUB,
@@ -5978,7 +5952,7 @@ void launch_star_tail(hipStream_t s, const ResolveArgs& a, const EnvView& env, c
                       int n_bound, int max_passes, int wgs_bound, int test_stall) {
   // (per call, for the CURRENT device: a process may hold contexts on several)
   const size_t lds = collide_lds_bytes(rob.n_tri, SEG_WAVES);
-  if (lds > 32 * 1024) (void)hipFuncSetAttribute(reinterpret_cast<const void*>(k_star_tail), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+  (void)set_dyn_lds(k_star_tail, lds, 32 * 1024);
   // resident at once: at most one workgroup per CU of an otherwise idle GPU; wgs_bound (SFFGPU_STAR_TAIL_WGS) bounds it further
   // (processes sharing one GPU: the sum of their grids must fit, or their barriers wait for each other until the time-out faults)
   int dev = 0, cus = 256;
@@ -6039,7 +6013,7 @@ void launch_round_collide(hipStream_t s, const sff::Knobs& kn, const EnvView& en
   if (!pose_hit) n_pose = 0;
   if (n_slots <= 0 && n_pose <= 0) return;
   size_t lds = collide_lds_bytes(rob.n_tri, SEG_WAVES);
-  if (lds > 48 * 1024) (void)hipFuncSetAttribute(reinterpret_cast<const void*>(k_collide_segments_dyn), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+  (void)set_dyn_lds(k_collide_segments_dyn, lds, 48 * 1024);
   // 2 workgroups of 4 waves per CU = what the exact kernel's register budget keeps resident (256 CUs)
   const int blocks = kn.seg_blocks ? kn.seg_blocks : 512;
   const int cull_blocks = kn.cull_blocks;

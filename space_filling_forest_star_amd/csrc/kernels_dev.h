@@ -1,4 +1,5 @@
-// kernels_dev.h — device-side helpers shared by kernels.hip and devforest.hip (neighbour-grid addressing).
+// kernels_dev.h — device-side helpers shared by kernels.hip, devforest.hip, devstar.hip and devprio.hip: neighbour-grid
+// addressing, the relaxed agent-scope loads / stores, the reference's integer draw, the top-k list, the sampler.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -36,6 +37,41 @@ __device__ __forceinline__ void grid_put(const GridView& g, const GridItem& it) 
       if (g.ovf_lite) g.ovf_lite[o] = lt;
     }
   }
+}
+
+// ---- relaxed agent-scope accesses (prio_heap_dev.h's hl_i32 / hl_f64 are the same loads under the heap's names)
+// sq_*: loads of forest state the launch may itself have written go past the vector L1 (`sc1` loads served by the L2 the
+// workgroup's stores write through to); the environment, the robot and the engine words are immutable while it runs.
+__device__ __forceinline__ int sq_i32(const int32_t* p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
+__device__ __forceinline__ unsigned long long sq_u64(const unsigned long long* p) {
+  return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+__device__ __forceinline__ double sq_f64(const double* p) {
+  return __longlong_as_double((long long)__hip_atomic_load(reinterpret_cast<const unsigned long long*>(p), __ATOMIC_RELAXED,
+                                                            __HIP_MEMORY_SCOPE_AGENT));
+}
+__device__ __forceinline__ int sq_u8(const uint8_t* p) { return (int)__hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
+__device__ __forceinline__ void sq_drain() { asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); }
+// wt_*: write-through stores - what one wavefront writes and a wavefront on another XCD reads in the same launch
+__device__ __forceinline__ void wt_i32(int32_t* p, int v) { __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
+__device__ __forceinline__ void wt_u64(unsigned long long* p, unsigned long long v) {
+  __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+__device__ __forceinline__ void wt_f64(double* p, double v) {
+  wt_u64(reinterpret_cast<unsigned long long*>(p), (unsigned long long)__double_as_longlong(v));
+}
+__device__ __forceinline__ void wt_u8(uint8_t* p, uint8_t v) { __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
+
+// libstdc++ uniform_int_distribution<int>(0, range - 1) on one 64-bit engine word (Lemire's multiply-shift):
+// returns the draw, or -1 when the word falls into the rejection zone (the reference then draws again)
+__device__ __forceinline__ int lemire_pick(unsigned long long word, unsigned long long range) {
+  const unsigned long long lo = word * range;
+  const unsigned long long hi = __umul64hi(word, range);
+  if (lo < range) {
+    const unsigned long long thr = (0ULL - range) % range;
+    if (lo < thr) return -1;
+  }
+  return (int)hi;
 }
 
 // ---- survivors of the clearance cull -> items of the exact kernel.  The lead lanes (lane % 8 == 0) of a step each hold one

@@ -1,6 +1,6 @@
 // rrt_seq_batch.inc - session batches: the one-by-one loop of ONE RRT / RRT* / Multi-T-RRT session on ONE wavefront
 // (kernels.h: RrtSeqArgs), included by kernels.hip behind the forest's loop, whose building blocks it strings together:
-// sq_lemire, sq_knn, pose_exact, sq_edge_clear_fast / sq_path_free, grid_put.  Reference: Solve()'s loop src/rrt.h:93-99 and
+// lemire_pick, sq_knn, pose_exact, sq_edge_clear_fast / sq_path_free, grid_put.  Reference: Solve()'s loop src/rrt.h:93-99 and
 // expandNode :128-322; on the host Rrt::run with wave == 1 and Rrt::expand.
 //
 // Evaluation is lazy exactly like the reference's - an edge is checked when the loop reaches it - so the reference-equivalent
@@ -99,7 +99,7 @@ __device__ __forceinline__ void rrt_seq_body(const RrtSeqArgs& A) {
     auto hand_over = [&](int why) { cursor = cur_a; cc = cc_a; pf = pf_a; nq = nq_a; iter = iter_a; status = SFFK_RRT_HOST_ITER; reason = why; };
     // ---- 1. the tree to expand (:95): uniform_int(0, numTrees) over the live-tree list, a rejected word draws again
     int pick;
-    do { pick = sq_lemire(A.ring[cursor & A.ring_mask], (unsigned long long)A.pick_range); ++cursor; } while (pick < 0 && cursor < A.words_end);
+    do { pick = lemire_pick(A.ring[cursor & A.ring_mask], (unsigned long long)A.pick_range); ++cursor; } while (pick < 0 && cursor < A.words_end);
     if (pick < 0) { cursor = cur_a; break; }
     ++iter;
     const int mine = A.live[pick];
@@ -339,10 +339,8 @@ __global__ __launch_bounds__(64) void k_rrt_seq_batch(const RrtSeqArgs* __restri
 hipError_t launch_rrt_seq_batch(hipStream_t s, const RrtSeqArgs* members_dev, int n, bool optimize, size_t lds) {
   if (n <= 0) return hipSuccess;
   const void* fn = optimize ? reinterpret_cast<const void*>(k_rrt_seq_batch<true>) : reinterpret_cast<const void*>(k_rrt_seq_batch<false>);
-  if (lds > 48 * 1024) {
-    const hipError_t e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    if (e != hipSuccess) return e;
-  }
+  const hipError_t e = set_dyn_lds(fn, lds, 48 * 1024);
+  if (e != hipSuccess) return e;
   if (optimize) hipLaunchKernelGGL(k_rrt_seq_batch<true>, dim3(n), dim3(64), lds, s, members_dev, n);
   else hipLaunchKernelGGL(k_rrt_seq_batch<false>, dim3(n), dim3(64), lds, s, members_dev, n);
   return hipGetLastError();

@@ -2,9 +2,11 @@
 // kernels.hip includes it in k_seq_waves<OPT> (`A` = the kernel's by-value argument) and in seq_waves_body<OPT> (`A` = a
 // reference; k_seq_waves_batch calls it on the workgroup's member of the argument array).  The single-forest entry includes
 // the text instead of calling the function because the call, inlined, changed the register allocation of its SFF* instance
-// (310 -> 536 scalar spills, - 3.6 % on its loop, measured); included, both its instances compile to exactly what they were.
+// (310 -> 536 scalar spills, - 3.6 % on its loop, measured); included, both its instances compiled, when the batch entry
+// came in, to exactly what they had been before it.
 // The batch entry is the other way round: through the function its SFF* instance spills 366 scalars, as included text 517
 // (- 11 %, measured).  Nothing in here looks at the workgroup's index.
+// lemire_pick and the sq_* loads are kernels_dev.h's.
 // PRIO (the template parameter beside OPT): the priority-frontier mode of a forest without a goal (src/forest.h:126-147,
 // 160-181, 360-363; PrioView).  The wave's node comes from a heap of a tree (pop / pop at a drawn index), an accepted node
 // is pushed onto every heap of its tree at once, an exhausted node leaves the tree's other heaps, an expanded one goes back
@@ -89,7 +91,7 @@
         bool dry = false;
         auto draw = [&](int range) -> int {      // RandGen::randomIntMinMax(0, range - 1); -1 = redraw (or out of words)
           if (at >= A.words_end) { dry = true; return -1; }
-          const int v = sq_lemire(f.ring[at & f.ring_mask], (unsigned long long)range);
+          const int v = lemire_pick(f.ring[at & f.ring_mask], (unsigned long long)range);
           ++at;
           return v;
         };
@@ -124,7 +126,7 @@
     if (PRIO && w_heap >= 0) node = hp_node;
     else {
       if (pool < 1) { terminated = 1; break; }
-      do { pick = sq_lemire(f.ring[cursor & f.ring_mask], (unsigned long long)pool); ++cursor; if (pick < 0) ++redraws; } while (pick < 0);
+      do { pick = lemire_pick(f.ring[cursor & f.ring_mask], (unsigned long long)pool); ++cursor; if (pick < 0) ++redraws; } while (pick < 0);
       node = sq_i32((use_closed ? f.closed : frontier) + pick);
     }
     ++waves;
