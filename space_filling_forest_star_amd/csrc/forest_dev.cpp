@@ -781,6 +781,8 @@ void Forest::sync_host() {
       for (int s = 0; s < k.n_slots; ++s) { slots[s].tree = stt[s]; slots[s].heap = sh[s]; slots[s].from_closed = false; }
     }
   }
+  // (a goal forest that ran in the loop of waves of one slot: Solver::connectedTrees as the wave's end leaves it, :196-201)
+  if (cfg.has_goal && batch_eligible() && !in_wave) max_connected();
   c.store_n = n;
   c.grid_inserted = n;
   d.host_nodes = n;
@@ -1312,7 +1314,9 @@ bool Forest::dev_wave_begin() {
 
 // waves of one slot the persistent single-wavefront loop can run (a member of run_forest_batch needs no more) ...
 bool Forest::batch_eligible() const {
-  return dev.on && cfg.wave == 1 && cfg.world == 1 && num_roots <= 64 && !cfg.has_goal && (!use_priority() || kn.prio_loop);
+  // (a goal: forests created under SFFGPU_GOAL_LOOP=1, and not together with the priority frontier)
+  if (cfg.has_goal && !(kn.goal_loop && !use_priority())) return false;
+  return dev.on && cfg.wave == 1 && cfg.world == 1 && num_roots <= 64 && (!use_priority() || kn.prio_loop);
 }
 // ... and sffgpu_forest_run takes that loop for them
 bool Forest::seq_eligible() const { return batch_eligible() && !kn.no_seq && !seq_suspended; }
@@ -1325,7 +1329,7 @@ bool Forest::seq_eligible() const { return batch_eligible() && !kn.no_seq && !se
 static const size_t SPEC_HEAD = 4096;   // bytes in front of the records: 4 x 64 control-block granules, the step word
 bool Forest::spec_setup() {
   DevEngine& d = dev;
-  if (d.spec_off || use_priority()) return false;   // (the priority frontier runs on the single wavefront)
+  if (d.spec_off || use_priority() || cfg.has_goal) return false;   // (the priority frontier and the goal mode run on the single wavefront)
   const int TM = std::max(1, cfg.threshold_misses);
   if (d.spec_n_sc > 0 && d.spec_tm == TM) return true;
   if (TM > 8) { d.spec_off = true; return false; }
@@ -1503,7 +1507,7 @@ void Forest::run_device_seq(int max_waves) {
       HIPCHK(hipMemsetAsync(d.spec_area.p, 0, d.spec_area.cap, c.stream));
       sffk::launch_spec_waves(c.stream, sa);
     } else {
-      sffk::launch_seq_waves(c.stream, a);
+      HIPCHK(sffk::launch_seq_waves(c.stream, a));
     }
     HIPCHK(hipMemcpyAsync(d.h_ctrl.as<sffk::DevCtrl>(), d.ctrl.p, sizeof(sffk::DevCtrl), hipMemcpyDeviceToHost, c.stream));
     d.status_copied[0] = true;

@@ -4446,12 +4446,12 @@ static hipError_t set_dyn_lds(K kernel, size_t lds, size_t threshold) {
 
 // the loop itself is seq_waves_body.inc.  k_seq_waves includes it as text, on its by-value argument, which keeps this entry's
 // code as it was before the loop was shared; seq_waves_body is the same loop as a function of a reference (k_seq_waves_batch)
-template <bool OPT, bool PRIO>
+template <bool OPT, bool PRIO, bool GOAL>
 __global__ __launch_bounds__(64) void k_seq_waves(SeqArgs A) {
 #include "seq_waves_body.inc"
 }
 
-template <bool OPT, bool PRIO>
+template <bool OPT, bool PRIO, bool GOAL>
 __device__ __forceinline__ void seq_waves_body(const SeqArgs& A) {
 #include "seq_waves_body.inc"
 }
@@ -4461,37 +4461,42 @@ __device__ __forceinline__ void seq_waves_body(const SeqArgs& A) {
 // local, so they live in scalar registers like the kernel arguments of k_seq_waves do.  A workgroup never waits for another
 // one - no step word, no records, no barrier across the grid - so, unlike k_spec_waves, no grid size can strand a workgroup:
 // what is not resident at once simply runs when a slot frees up.
-template <bool OPT, bool PRIO>
+template <bool OPT, bool PRIO, bool GOAL>
 __global__ __launch_bounds__(64) void k_seq_waves_batch(const SeqArgs* __restrict__ members, int n) {
   if ((int)blockIdx.x >= n) return;
-  seq_waves_body<OPT, PRIO>(members[blockIdx.x]);
+  seq_waves_body<OPT, PRIO, GOAL>(members[blockIdx.x]);
 }
 
-template <bool OPT, bool PRIO>
+template <bool OPT, bool PRIO, bool GOAL>
 static hipError_t launch_seq_waves_batch_as(hipStream_t s, const SeqArgs* members_dev, int n, size_t lds) {
-  const hipError_t e = set_dyn_lds(k_seq_waves_batch<OPT, PRIO>, lds, 48 * 1024);
+  const hipError_t e = set_dyn_lds(k_seq_waves_batch<OPT, PRIO, GOAL>, lds, 48 * 1024);
   if (e != hipSuccess) return e;
-  hipLaunchKernelGGL((k_seq_waves_batch<OPT, PRIO>), dim3(n), dim3(64), lds, s, members_dev, n);
+  hipLaunchKernelGGL((k_seq_waves_batch<OPT, PRIO, GOAL>), dim3(n), dim3(64), lds, s, members_dev, n);
   return hipGetLastError();
 }
-hipError_t launch_seq_waves_batch(hipStream_t s, const SeqArgs* members_dev, int n, bool optimize, bool priority, size_t lds) {
+hipError_t launch_seq_waves_batch(hipStream_t s, const SeqArgs* members_dev, int n, bool optimize, bool priority, bool goal, size_t lds) {
   if (n <= 0) return hipSuccess;
-  if (priority) return optimize ? launch_seq_waves_batch_as<true, true>(s, members_dev, n, lds) : launch_seq_waves_batch_as<false, true>(s, members_dev, n, lds);
-  return optimize ? launch_seq_waves_batch_as<true, false>(s, members_dev, n, lds) : launch_seq_waves_batch_as<false, false>(s, members_dev, n, lds);
+  if (priority && goal) return hipErrorInvalidValue;   // (no such instance: priority + goal is the host-replay engine's)
+  if (goal) return optimize ? launch_seq_waves_batch_as<true, false, true>(s, members_dev, n, lds) : launch_seq_waves_batch_as<false, false, true>(s, members_dev, n, lds);
+  if (priority) return optimize ? launch_seq_waves_batch_as<true, true, false>(s, members_dev, n, lds) : launch_seq_waves_batch_as<false, true, false>(s, members_dev, n, lds);
+  return optimize ? launch_seq_waves_batch_as<true, false, false>(s, members_dev, n, lds) : launch_seq_waves_batch_as<false, false, false>(s, members_dev, n, lds);
 }
 
 #include "rrt_seq_batch.inc"
 
-template <bool OPT, bool PRIO>
+template <bool OPT, bool PRIO, bool GOAL>
 static void launch_seq_waves_as(hipStream_t s, const SeqArgs& a, size_t lds) {
-  (void)set_dyn_lds(k_seq_waves<OPT, PRIO>, lds, 48 * 1024);
-  hipLaunchKernelGGL((k_seq_waves<OPT, PRIO>), dim3(1), dim3(64), lds, s, a);
+  (void)set_dyn_lds(k_seq_waves<OPT, PRIO, GOAL>, lds, 48 * 1024);
+  hipLaunchKernelGGL((k_seq_waves<OPT, PRIO, GOAL>), dim3(1), dim3(64), lds, s, a);
 }
-void launch_seq_waves(hipStream_t s, const SeqArgs& a) {
+hipError_t launch_seq_waves(hipStream_t s, const SeqArgs& a) {
   const size_t lds = collide_lds_bytes(a.rob.n_tri, 1);
-  if (a.f.prio.n_heaps > 0) { if (a.optimize) launch_seq_waves_as<true, true>(s, a, lds); else launch_seq_waves_as<false, true>(s, a, lds); }
-  else if (a.optimize) launch_seq_waves_as<true, false>(s, a, lds);
-  else launch_seq_waves_as<false, false>(s, a, lds);
+  if (a.f.goal_id >= 0 && a.f.prio.n_heaps > 0) return hipErrorInvalidValue;   // (no such instance, as in launch_seq_waves_batch)
+  if (a.f.goal_id >= 0) { if (a.optimize) launch_seq_waves_as<true, false, true>(s, a, lds); else launch_seq_waves_as<false, false, true>(s, a, lds); }
+  else if (a.f.prio.n_heaps > 0) { if (a.optimize) launch_seq_waves_as<true, true, false>(s, a, lds); else launch_seq_waves_as<false, true, false>(s, a, lds); }
+  else if (a.optimize) launch_seq_waves_as<true, false, false>(s, a, lds);
+  else launch_seq_waves_as<false, false, false>(s, a, lds);
+  return hipSuccess;
 }
 
 // ------------------------------------------------------------------ waves of one slot, SPECULATED (kernels.h: SpecArgs)

@@ -43,6 +43,9 @@ struct Knobs {
   bool prio_seq = false;            // SFFGPU_PRIO_SEQ=1 (tests): picks by the sequential k_prio_begin instead of k_prio_plan
   bool prio_loop = false;           // SFFGPU_PRIO_LOOP=1: a priority-frontier forest without a goal of waves of ONE slot runs on the device, in the
                                     // single-wavefront loop (k_seq_waves<., true>), and may be a member of a forest batch; 0 = the host-replay engine
+  bool goal_loop = false;           // SFFGPU_GOAL_LOOP=1: a single-goal forest (has_goal, no priority frontier) of waves of ONE slot runs in the
+                                    // single-wavefront loop (k_seq_waves<., false, true>) and may be a member of a forest batch; 0 = the round engine,
+                                    // the solving wave replayed on the host
   bool no_order = false;            // SFFGPU_NO_ORDER=1: a round's samples by index instead of in the wave's spatial order (sffk::OrderView)
   int order_min_wave = 4096;        // SFFGPU_ORDER_MIN_WAVE (>= 2): smallest wave that uses the order
   int test_hitcap = 64;             // SFFGPU_TEST_HITCAP (1..64: one lane per hit), tests: device hit list

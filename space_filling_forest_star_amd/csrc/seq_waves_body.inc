@@ -13,6 +13,13 @@
 // onto its own - the heap routines of prio_heap_dev.h, on this one wavefront.  Heap sizes and, per tree, the number of
 // non-empty heaps are kept in LDS (and written through to PrioView::size); the frontier list is not used.  Everything of
 // the mode stands in `if constexpr (PRIO)`: the instances without it compile to what they were.
+// GOAL (the third template parameter; never together with PRIO): Problem::hasGoal, the single-query mode (src/forest.h:91-109,
+// 196-201, 283-299, 369-372; f.goal_id = the goal's node, the one node of tree R - 1, never on the frontier or the closed
+// list).  A qualifying neighbour of another tree rejects the attempt without an edge check unless it is the goal; the goal
+// costs one isPathFree(newPoint, goal), and a free one makes the attempt the solving one: it is appended like any accepted
+// attempt (SFF*: choose parent and rewires as usual), one border (new node, goal) is written behind it, solved ends the
+// loop.  Nothing else solves a goal forest: the connectivity test at a wave's end does not run.  Everything of the mode
+// stands in `if constexpr (GOAL)`.
   extern __shared__ double lds_d[];
   __shared__ int32_t s_fh, s_ovf;
   __shared__ int32_t h_id[64], h_tree[64];
@@ -195,6 +202,8 @@
       lap(3);
       const double pdist = dist6(cpos, qp);                        // parentDistance, :250
       int n_hit = 0;
+      [[maybe_unused]] bool solving = false;                       // GOAL: this attempt saw the goal over a free edge (:287)
+      [[maybe_unused]] double gpos[6] = {0, 0, 0, 0, 0, 0};
       if (!flt && !reject) {
         nq += (unsigned long long)R;                               // :262-267 one radiusSearch per tree
         // ---- the neighbours: exact 6-D ball of radius max(parentDistance, treeDistance) from the cells its box touches
@@ -284,6 +293,17 @@
           const int s_same = __shfl((int)same, src), s_id = __shfl(id, src), s_tree = __shfl(t, src);
           double np6[6];
           for (int k = 0; k < 6; ++k) np6[k] = h_pos[6 * src + k];
+          if constexpr (GOAL) {
+            if (!s_same) {                                         // :283-299 with a goal: no border list, no edge but the goal's
+              if (s_id != f.goal_id) { reject = true; break; }
+              pf += 1; ex_seg += 1;
+              const bool fr = (sq_edge_clear_fast(A.env, qp, np6, lane, cc, ex_smp) || sq_path_free(A.env, A.rob, rtri, stack, cand, queue, stage, qp, np6, &s_fh, &s_ovf, lane, cc, ex_smp, flt));
+              // :296 not rejected: the walk goes on (and ends here: the goal's tree is the last one and holds this one node)
+              if (fr && !flt) { solving = true; for (int k = 0; k < 6; ++k) gpos[k] = np6[k]; }
+              else reject = true;
+              continue;
+            }
+          }
           pf += 1; ex_seg += 1;
           if (s_same) {
             const bool fr = (sq_edge_clear_fast(A.env, np6, qp, lane, cc, ex_smp) || sq_path_free(A.env, A.rob, rtri, stack, cand, queue, stage, np6, qp, &s_fh, &s_ovf, lane, cc, ex_smp, flt));
@@ -432,6 +452,30 @@
         }
         sq_drain();
       }
+      if constexpr (GOAL) {
+        if (solving) {   // :369-372 the one border of a goal forest: (new node, goal), cost after choose-parent
+          const int gid = f.goal_id;
+          const int a = gid < idn ? gid : idn, b = gid < idn ? idn : gid;
+          const unsigned long long key = ((unsigned long long)(uint32_t)a << 32) | ((unsigned long long)(uint32_t)b + 1ULL);
+          size_t h = (size_t)((key * 0x9E3779B97F4A7C15ULL) >> 17) & (size_t)f.bt_mask;
+          for (int guard = 0; guard < (1 << 24); ++guard) {        // (the new node has no entry yet: the first free slot)
+            if (sq_u64(f.bt_key + h) == 0ULL) break;
+            h = (h + 1) & (size_t)f.bt_mask;
+          }
+          if (lane == 0) {
+            f.bt_key[h] = key;
+            f.bt_val[h] = c->epoch << 32;
+            f.b_n1[nb] = a; f.b_n2[nb] = b;
+            f.b_ta[nb] = mine; f.b_tb[nb] = R - 1;
+            f.b_dist[nb] = best + dist6(qp, gpos);
+            f.pair[(size_t)(R - 1) * R + mine] = 1;
+            f.pair[(size_t)mine * R + (R - 1)] = 1;
+          }
+          sq_drain();
+          ++nb;
+          solved = 1;
+        }
+      }
       lap(6);
     }
     if (fault) break;
@@ -486,7 +530,9 @@
     sq_drain();
     // ---- termination (:184-201)
     empty_frontier = PRIO ? (total_ne == 0 ? 1 : 0) : (fn == 0 ? 1 : 0);   // (PRIO: every heap of every tree is empty, :184-191)
-    if (!solved && empty_frontier) {
+    bool conn_test = !solved && empty_frontier;
+    if constexpr (GOAL) conn_test = false;   // :198 with a goal only reaching it solves
+    if (conn_test) {
       // maxConnected() == numRoots: every tree reachable from tree 0 over pairs that hold a border (R <= 64: a lane per tree)
       unsigned long long reach = 1ULL, frontier_set = 1ULL;
       if (R <= 64) {
