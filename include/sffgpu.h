@@ -170,10 +170,11 @@ int sffgpu_forest_run(sffgpu_forest* f, int max_waves);
  * one kernel launch for all of them.  Every forest ends exactly as sffgpu_forest_run(f[i], max_waves) would leave it.
  * Members: device engine, wave == 1, world == 1, no goal, at most 64 roots, SFF or SFF*; a member with a priority_bias
  * qualifies when its forest was CREATED with SFFGPU_PRIO_LOOP=1 in the environment, a member with a goal (has_goal, no
- * priority_bias) when it was CREATED with SFFGPU_GOAL_LOOP=1 (both default 0: the member is refused; a goal together with
- * a priority_bias is always refused).  A goal member ends at the iteration that reaches its goal, like sffgpu_forest_run.
- * The kinds of one batch (SFF / SFF*; plain, priority frontier or single goal) go out as up to six launches.  All members
- * on one device, each on a context of its own (a context owns one node store).
+ * priority_bias) when it was CREATED with SFFGPU_GOAL_LOOP=1, a member with a goal AND a priority_bias when it was CREATED
+ * with SFFGPU_PRIO_GOAL_LOOP=1 - that knob alone, the other two do not cover it (all three default 0: the member is
+ * refused).  A goal member ends at the iteration that reaches its goal, like sffgpu_forest_run.  The kinds of one batch
+ * (SFF / SFF*; plain, priority frontier, single goal, priority + goal) go out as up to eight launches.  All members on one
+ * device, each on a context of its own (a context owns one node store).
  * SFFGPU_ERR_ARG, before anything has run: a member that does not qualify, two members of one context, the same forest
  * twice, n <= 0, f == NULL.  When a member fails, its error code is returned, *failed is its index (-1 otherwise) and
  * the message is on ITS context; every other member has been left after a whole number of launches - consistent, and

@@ -815,7 +815,7 @@ def run_batch(forests, max_waves=0):
         elif rc == -1:
             msg += ": not a batch (needs n >= 1 forests with wave == 1, world == 1, the device engine, at most 64 roots, each on a" \
                    " context of its own, all on one device; a priority_bias only in a forest created under SFFGPU_PRIO_LOOP=1," \
-                   " a goal only in one created under SFFGPU_GOAL_LOOP=1, never both)"
+                   " a goal only in one created under SFFGPU_GOAL_LOOP=1, both only in one created under SFFGPU_PRIO_GOAL_LOOP=1)"
         raise SffGpuError(msg)
 
 

@@ -197,7 +197,7 @@ int sffgpu_forest_run(sffgpu_forest* f, int max_waves) {
   return f->f->need_host_exchange ? SFFGPU_NEED_HOST_EXCHANGE : SFFGPU_OK;
 }
 // (members: Forest::batch_eligible - waves of one slot on the device engine; a priority bias needs SFFGPU_PRIO_LOOP=1 at the
-// forest's creation, a goal SFFGPU_GOAL_LOOP=1, the two together never qualify)
+// forest's creation, a goal SFFGPU_GOAL_LOOP=1, the two together SFFGPU_PRIO_GOAL_LOOP=1 and neither of the others)
 int sffgpu_forest_run_batch(sffgpu_forest* const* f, int n, int max_waves, int32_t* failed) {
   return run_batch_entry(f, n, failed, [](const Forest& m) { return m.batch_eligible(); },
                          [&](Forest* const* m, int* bad) { run_forest_batch(m, n, max_waves, bad); });

@@ -543,7 +543,7 @@ struct Forest {
 };
 
 // Forest batches (forest_batch.cpp; the lock step: batch_lockstep.h): n independent forests of waves of ONE slot, each on a context of its own, advanced in
-// lock step - one wavefront per forest, one launch of k_seq_waves_batch per kind (SFF / SFF*; plain, priority frontier or single goal) for all of them - until each
+// lock step - one wavefront per forest, one launch of k_seq_waves_batch per kind (SFF / SFF*; plain, priority frontier, single goal, or priority + goal) for all of them - until each
 // has terminated or run max_waves waves (0 = no bound).  The caller has checked the members (batch_eligible, distinct
 // contexts, one device).  A member that throws ends the call: *failed = its index, the exception goes on to the caller;
 // every other member has been taken in after a whole number of launches.

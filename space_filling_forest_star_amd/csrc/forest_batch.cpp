@@ -7,8 +7,8 @@
 // here is what is a forest's own in it:
 //   - a member is live until it has terminated or run its max_waves; one a host-engine wave was left unfinished in (in_wave)
 //     is advanced on its own through run_device(1) first, as run_device_seq does, and joins the same step;
-//   - six kinds (SFF / SFF*; plain, priority frontier or single goal: the template instances of the kernel), at most 4 096
-//     waves a launch;
+//   - eight kinds (SFF / SFF*; plain, priority frontier, single goal, or priority + goal: the template instances of the
+//     kernel), at most 4 096 waves a launch;
 //   - a member is taken in exactly like a single forest: dev_finish_wave (growth, re-celling) and, after a list fault,
 //     that one wave on the host-replay engine (seq_lists_fault).
 #include "batch_lockstep.h"
@@ -18,8 +18,8 @@ namespace sff {
 namespace {
 struct ForestFamily {
   using Args = sffk::SeqArgs;
-  // the template instance that runs a member: bit 0 SFF*, bit 1 priority frontier, bit 2 single goal (never with bit 1)
-  static constexpr int n_kinds = 6;
+  // the template instance that runs a member: bit 0 SFF*, bit 1 priority frontier, bit 2 goal
+  static constexpr int n_kinds = 8;
   Forest* const* m;
   int n, max_waves;
   std::vector<uint64_t> w0, w_launch;
@@ -58,7 +58,7 @@ struct ForestFamily {
     w_launch[i] = m[i]->dev.last.waves;
     return m[i]->seq_prepare(waves);
   }
-  int kind(int i) { return (m[i]->cfg.optimize ? 1 : 0) | (m[i]->use_priority() ? 2 : m[i]->cfg.has_goal ? 4 : 0); }
+  int kind(int i) { return (m[i]->cfg.optimize ? 1 : 0) | (m[i]->use_priority() ? 2 : 0) | (m[i]->cfg.has_goal ? 4 : 0); }
   hipStream_t stream(int i) { return m[i]->ctx->stream; }
   StatusBlock status(int i) { return {m[i]->dev.h_ctrl.p, m[i]->dev.ctrl.p, sizeof(sffk::DevCtrl)}; }
   hipError_t launch(hipStream_t s, const Args* a, int count, int kind, size_t lds) {

@@ -36,14 +36,24 @@ static uint64_t next_pow2(uint64_t v) {
 
 bool Forest::device_eligible() const {
   // plain SFF and SFF* (choose-parent + rewire on the device: devstar.hip), the single-goal mode, and the priority-frontier
-  // mode without a goal (heaps in HBM, one workgroup per heap: devprio.hip); priority + goal runs on the host-replay engine
+  // mode without a goal (heaps in HBM, one workgroup per heap: devprio.hip); priority + goal runs on the host-replay engine,
+  // except in waves of ONE slot under SFFGPU_PRIO_GOAL_LOOP=1 (below)
   if (!use_priority()) return true;
+  if (cfg.has_goal) {
+    // priority + goal: the single-wavefront loop only (k_seq_waves<., true, true>), so waves of one slot, one rank, a lane
+    // per tree, and only for a forest created under SFFGPU_PRIO_GOAL_LOOP=1 - neither SFFGPU_PRIO_LOOP nor SFFGPU_GOAL_LOOP
+    // covers the combination.  One heap per start tree (src/forest.h:104-108), none for the goal's tree.
+    if (!kn.prio_goal_loop || !kn.prio_device || kn.no_seq || num_roots > 64 || cfg.wave != 1 || cfg.world > 1) return false;
+    const long long heaps_n = num_roots - 1;
+    const long long cap = (long long)std::max(cfg.node_budget, 4096) + 2LL * cfg.wave + 128;
+    return heaps_n >= 1 && heaps_n <= SFFK_PRIO_MAX_HEAPS && heaps_n * cap * 16 <= (32LL << 30);
+  }
   // (measured on dense_3D, 100 k nodes: 73 k nodes/s at waves of 64 slots against the host engine's 29 k, 0.83 M at 1 024
   // against 98 k, 1.6 M at 8 192; waves of one slot - the reference's own loop - stay on the host engine unless the forest
   // was created under SFFGPU_PRIO_LOOP=1, which gives them to the single-wavefront loop (k_seq_waves<., true>);
   // SFFGPU_PRIO_DEVICE=0 keeps the whole mode there)
   const int min_wave = !kn.prio_device ? 0x7fffffff : (kn.prio_loop && !kn.no_seq && num_roots <= 64) ? 1 : 2;
-  if (cfg.has_goal || cfg.wave < min_wave || cfg.world > 1) return false;
+  if (cfg.wave < min_wave || cfg.world > 1) return false;
   const long long heaps_n = (long long)num_roots * (num_roots - 1);
   const long long cap = (long long)std::max(cfg.node_budget, 4096) + 2LL * cfg.wave + 128;
   return heaps_n >= 1 && heaps_n <= SFFK_PRIO_MAX_HEAPS && heaps_n * cap * 16 <= (32LL << 30);   // (ids + keys + position map)
@@ -1314,8 +1324,10 @@ bool Forest::dev_wave_begin() {
 
 // waves of one slot the persistent single-wavefront loop can run (a member of run_forest_batch needs no more) ...
 bool Forest::batch_eligible() const {
-  // (a goal: forests created under SFFGPU_GOAL_LOOP=1, and not together with the priority frontier)
-  if (cfg.has_goal && !(kn.goal_loop && !use_priority())) return false;
+  // (a goal: forests created under SFFGPU_GOAL_LOOP=1; a goal together with the priority frontier: under
+  // SFFGPU_PRIO_GOAL_LOOP=1 and nothing else - device_eligible() has checked the rest of it)
+  if (cfg.has_goal && use_priority()) return dev.on && kn.prio_goal_loop && cfg.wave == 1 && cfg.world == 1 && num_roots <= 64;
+  if (cfg.has_goal && !kn.goal_loop) return false;
   return dev.on && cfg.wave == 1 && cfg.world == 1 && num_roots <= 64 && (!use_priority() || kn.prio_loop);
 }
 // ... and sffgpu_forest_run takes that loop for them
@@ -1572,6 +1584,18 @@ void Forest::run_device_seq(int max_waves) {
 
 void Forest::run_device(int max_waves) {
   if (seq_eligible()) { run_device_seq(max_waves); return; }
+  if (use_priority() && cfg.has_goal) {
+    // priority + goal is the loop's alone (device_eligible): what gets here is a wave the host-replay engine left half done
+    // (run_device_seq / run_forest_batch, seq_suspended), and the round engine has no such mode - that engine finishes it
+    dev_to_host();
+    while (in_wave) {
+      round_begin();
+      int32_t cnt = (int32_t)records.size();
+      round_commit(records.data(), cnt, &cnt, 1);
+    }
+    dev_upload_state();
+    return;
+  }
   Ctx& c = *ctx;
   DevEngine& d = dev;
   HIPCHK(hipSetDevice(c.device));

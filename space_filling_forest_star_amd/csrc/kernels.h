@@ -626,9 +626,10 @@ void launch_prio_index(hipStream_t s, const PrioView& p);
 // ---- waves of ONE slot = the reference's own loop order (src/forest.h:122-202): one persistent wavefront runs whole
 // outer iterations - frontier pick, up to ThresholdMisses x (sample, pose check, parent edge, 27-cell neighbour query,
 // the neighbour edges in the order the reference reaches them, append), closed list / frontier erase, termination - for as
-// many waves as the engine words last, instead of ~33 launches per wave.  Plain SFF, SFF* and, for a forest without a goal,
-// the priority-frontier mode (f.prio.n_heaps > 0: the PRIO instances, seq_waves_body.inc); or, without the priority
-// frontier, the single-goal mode (f.goal_id >= 0: the GOAL instances - reaching the goal ends the loop).  Evaluation is lazy exactly like
+// many waves as the engine words last, instead of ~33 launches per wave.  Plain SFF, SFF*, the priority-frontier mode
+// (f.prio.n_heaps > 0: the PRIO instances, seq_waves_body.inc), the single-goal mode (f.goal_id >= 0: the GOAL instances -
+// reaching the goal ends the loop), and the two together (<., true, true>: one heap per start tree, keyed by the distance
+// to the goal).  Evaluation is lazy exactly like
 // the reference's (an edge is only checked when the loop gets to it), so the reference-equivalent counters ARE the
 // executed ones.  Stops early (halt + fault in the control block, the faulted attempt rolled back) where the round
 // engine would: a bounded list overflowed, arrays / border table to grow, the grid's overflow list to re-cell.
@@ -654,11 +655,11 @@ struct SeqArgs {
   // accepted, ThresholdMisses = none), nodes} - 8 ints, indexed by the launch's wave number; null = off
   int32_t* trace; int trace_cap;
 };
-// hipErrorInvalidValue, nothing launched: priority frontier and goal together (no such instance); hipSuccess otherwise
+// picks the instance from a.optimize, a.f.prio.n_heaps > 0 and a.f.goal_id >= 0 (every combination has one); hipSuccess
 hipError_t launch_seq_waves(hipStream_t s, const SeqArgs& a);
 // Forest batches (k_seq_waves_batch): n independent forests in one launch, workgroup b = one wavefront = members_dev[b]'s
 // loop.  All members of a launch are of one kind (optimize: SFF*; priority: the priority-frontier mode, f.prio.n_heaps > 0
-// in every member; goal: the single-goal mode, f.goal_id >= 0 in every member - not together with priority), lds = the
+// in every member; goal: the single-goal mode, f.goal_id >= 0 in every member; both: priority + goal), lds = the
 // largest collide_lds_bytes(rob.n_tri, 1) among them.  Returns the first error of setting the kernel's attribute or of the
 // launch itself.
 hipError_t launch_seq_waves_batch(hipStream_t s, const SeqArgs* members_dev, int n, bool optimize, bool priority, bool goal, size_t lds);

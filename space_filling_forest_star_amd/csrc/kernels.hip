@@ -4476,7 +4476,7 @@ static hipError_t launch_seq_waves_batch_as(hipStream_t s, const SeqArgs* member
 }
 hipError_t launch_seq_waves_batch(hipStream_t s, const SeqArgs* members_dev, int n, bool optimize, bool priority, bool goal, size_t lds) {
   if (n <= 0) return hipSuccess;
-  if (priority && goal) return hipErrorInvalidValue;   // (no such instance: priority + goal is the host-replay engine's)
+  if (priority && goal) return optimize ? launch_seq_waves_batch_as<true, true, true>(s, members_dev, n, lds) : launch_seq_waves_batch_as<false, true, true>(s, members_dev, n, lds);
   if (goal) return optimize ? launch_seq_waves_batch_as<true, false, true>(s, members_dev, n, lds) : launch_seq_waves_batch_as<false, false, true>(s, members_dev, n, lds);
   if (priority) return optimize ? launch_seq_waves_batch_as<true, true, false>(s, members_dev, n, lds) : launch_seq_waves_batch_as<false, true, false>(s, members_dev, n, lds);
   return optimize ? launch_seq_waves_batch_as<true, false, false>(s, members_dev, n, lds) : launch_seq_waves_batch_as<false, false, false>(s, members_dev, n, lds);
@@ -4491,8 +4491,8 @@ static void launch_seq_waves_as(hipStream_t s, const SeqArgs& a, size_t lds) {
 }
 hipError_t launch_seq_waves(hipStream_t s, const SeqArgs& a) {
   const size_t lds = collide_lds_bytes(a.rob.n_tri, 1);
-  if (a.f.goal_id >= 0 && a.f.prio.n_heaps > 0) return hipErrorInvalidValue;   // (no such instance, as in launch_seq_waves_batch)
-  if (a.f.goal_id >= 0) { if (a.optimize) launch_seq_waves_as<true, false, true>(s, a, lds); else launch_seq_waves_as<false, false, true>(s, a, lds); }
+  if (a.f.goal_id >= 0 && a.f.prio.n_heaps > 0) { if (a.optimize) launch_seq_waves_as<true, true, true>(s, a, lds); else launch_seq_waves_as<false, true, true>(s, a, lds); }
+  else if (a.f.goal_id >= 0) { if (a.optimize) launch_seq_waves_as<true, false, true>(s, a, lds); else launch_seq_waves_as<false, false, true>(s, a, lds); }
   else if (a.f.prio.n_heaps > 0) { if (a.optimize) launch_seq_waves_as<true, true, false>(s, a, lds); else launch_seq_waves_as<false, true, false>(s, a, lds); }
   else if (a.optimize) launch_seq_waves_as<true, false, false>(s, a, lds);
   else launch_seq_waves_as<false, false, false>(s, a, lds);

@@ -57,6 +57,7 @@ Knobs Knobs::from_env() {
   k.prio_seq = flag("SFFGPU_PRIO_SEQ", k.prio_seq);
   k.prio_loop = flag("SFFGPU_PRIO_LOOP", k.prio_loop);
   k.goal_loop = flag("SFFGPU_GOAL_LOOP", k.goal_loop);
+  k.prio_goal_loop = flag("SFFGPU_PRIO_GOAL_LOOP", k.prio_goal_loop);
   k.no_order = flag("SFFGPU_NO_ORDER", k.no_order);
   k.order_min_wave = int_in("SFFGPU_ORDER_MIN_WAVE", k.order_min_wave, 2);
   k.test_hitcap = int_in("SFFGPU_TEST_HITCAP", k.test_hitcap, 1, 64);

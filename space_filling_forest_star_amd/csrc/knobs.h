@@ -46,6 +46,9 @@ struct Knobs {
   bool goal_loop = false;           // SFFGPU_GOAL_LOOP=1: a single-goal forest (has_goal, no priority frontier) of waves of ONE slot runs in the
                                     // single-wavefront loop (k_seq_waves<., false, true>) and may be a member of a forest batch; 0 = the round engine,
                                     // the solving wave replayed on the host
+  bool prio_goal_loop = false;      // SFFGPU_PRIO_GOAL_LOOP=1: a forest with BOTH a goal and a priority bias (one heap per start tree, keyed by the distance
+                                    // to the goal) of waves of ONE slot runs in the single-wavefront loop (k_seq_waves<., true, true>) and may be a member
+                                    // of a forest batch; 0 = the host-replay engine.  Neither prio_loop nor goal_loop covers the combination
   bool no_order = false;            // SFFGPU_NO_ORDER=1: a round's samples by index instead of in the wave's spatial order (sffk::OrderView)
   int order_min_wave = 4096;        // SFFGPU_ORDER_MIN_WAVE (>= 2): smallest wave that uses the order
   int test_hitcap = 64;             // SFFGPU_TEST_HITCAP (1..64: one lane per hit), tests: device hit list

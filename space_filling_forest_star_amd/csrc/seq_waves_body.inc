@@ -13,13 +13,21 @@
 // onto its own - the heap routines of prio_heap_dev.h, on this one wavefront.  Heap sizes and, per tree, the number of
 // non-empty heaps are kept in LDS (and written through to PrioView::size); the frontier list is not used.  Everything of
 // the mode stands in `if constexpr (PRIO)`: the instances without it compile to what they were.
-// GOAL (the third template parameter; never together with PRIO): Problem::hasGoal, the single-query mode (src/forest.h:91-109,
+// GOAL (the third template parameter): Problem::hasGoal, the single-query mode (src/forest.h:91-109,
 // 196-201, 283-299, 369-372; f.goal_id = the goal's node, the one node of tree R - 1, never on the frontier or the closed
 // list).  A qualifying neighbour of another tree rejects the attempt without an edge check unless it is the goal; the goal
 // costs one isPathFree(newPoint, goal), and a free one makes the attempt the solving one: it is appended like any accepted
 // attempt (SFF*: choose parent and rewires as usual), one border (new node, goal) is written behind it, solved ends the
 // loop.  Nothing else solves a goal forest: the connectivity test at a wave's end does not run.  Everything of the mode
 // stands in `if constexpr (GOAL)`.
+// PRIO && GOAL: the two compose.  A start tree has ONE heap, keyed by the distance to the goal (src/forest.h:104-108); the
+// goal's tree R - 1 has none (PrioView::base[R - 1] == base[R], p_tne[R - 1] stays 0), so a tree draw - over all R trees,
+// :128 - that lands on it is redrawn like any tree whose heaps are empty, and the heap draw, randomIntMinMax(0, 0), still
+// takes its engine word (lemire_pick(word, 1) is 0 for every word).  The neighbour loop and the solving attempt are GOAL's,
+// the pick, the pushes and the wave's end PRIO's: empty_frontier is "every heap empty", with every heap empty the picks are
+// closed-list picks (w_heap < 0, prio_wave 0) whose children fill the heaps again, and a list fault - the goal's edge check
+// included - leaves the wave as PRIO leaves it, for the host-replay engine, which knows both modes.  Only one thing is
+// particular to the pair, an `if constexpr (!GOAL)` inside PRIO's wave end: an exhausted node has no other heap to leave.
   extern __shared__ double lds_d[];
   __shared__ int32_t s_fh, s_ovf;
   __shared__ int32_t h_id[64], h_tree[64];
@@ -487,6 +495,7 @@
       if (w_heap >= 0) {
         const PrioView& P = f.prio;
         if (failing) {
+          if constexpr (!GOAL) {
           const int b0 = P.base[w_tree], nh = P.base[w_tree + 1] - b0;
           const int at_v = lane < nh ? hl_i32(P.pos + (size_t)(b0 + lane) * P.cap + node) : -1;
           for (int j = 0; j < nh; ++j) {
@@ -497,6 +506,7 @@
             heap_remove(hr, node, hint);
             p_resize(w_tree, b0 + j, was, hr.n);
           }
+          }   // (GOAL: the tree's one heap is the one the node was popped from - nothing to leave, :165-175)
           const int fl = sq_u8(f.nflag + node);
           if (!(fl & 1)) {
             if (lane == 0) { f.nflag[node] = (uint8_t)((fl & ~2) | 1); f.closed[cn] = node; }
