@@ -244,11 +244,14 @@ int sffgpu_rrt_create(sffgpu_ctx* ctx, const sffgpu_rrt_cfg* cfg, const double* 
 void sffgpu_rrt_destroy(sffgpu_rrt* r);
 int sffgpu_rrt_run(sffgpu_rrt* r, int max_iterations); /* 0 = until solved / Problem::maxIterations */
 /* Session batches: n independent RRT / RRT* / Multi-T-RRT sessions advanced together, one wavefront per session, one launch
- * of the batch kernel per kind (RRT / RRT*) for all of them.  max_iterations means per member what it means for
+ * of the batch kernel per kind (RRT / RRT* / lazy RRT / lazy RRT*) for all of them.  max_iterations means per member what it means for
  * sffgpu_rrt_run.  Every member ends exactly as sffgpu_rrt_run(r[i], max_iterations) with cfg.wave == 1 would leave it:
  * nodes, links, merged tree membership, paths, the reference-equivalent counters and rng_draws; waves / speculated /
  * committed are not touched, batch_launches and batch_host_iterations are.  Members: dim 2 or 6, RRT or RRT*, any root
- * count, with or without goal and goal bias, any cfg.wave (it only steers sffgpu_rrt_run); NOT lazy_edge sessions; every
+ * count, with or without goal and goal bias, any cfg.wave (it only steers sffgpu_rrt_run); a lazy_edge session if and only
+ * if it was CREATED with SFFGPU_LAZY_BATCH=1 in the environment (default 0; the environment at the time of this call does not
+ * matter) - it leaves the batch when a new node reaches its goal, with solved, lazy_distance and the plan of
+ * sffgpu_rrt_lazy_plan as sffgpu_rrt_run leaves them; every
  * member on a context of its own (a context owns one node store), all on one device.  A call that breaks a rule returns
  * SFFGPU_ERR_ARG before anything runs.  If a member fails, *failed = its index (-1 otherwise) and the message is on ITS
  * context; every other member has been left after a whole number of launches - consistent, and free to run on, alone or in

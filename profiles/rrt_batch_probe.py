@@ -1,6 +1,7 @@
 """Session batches against what a user could do before them: B independent RRT / RRT* / Multi-T-RRT sessions of the
 bench's job shape (dense_3D, 6-DoF, the scenario's tree / sampling distances, the iteration budget of the bench's RRT legs,
-seeds 1..B; 1 root for RRT and RRT*, 10 roots for Multi-T-RRT).
+seeds 1..B; 1 root for RRT and RRT*, 10 roots for Multi-T-RRT; `lazy` / `lazy_star`: lazy edges - LazyTSP::runRRT, one root,
+goal = the second of the job's free points, sessions created under SFFGPU_LAZY_BATCH=1 - which end when they reach the goal).
 
 Legs (every repeat of every leg is a child process of its own, legs alternated inside one command):
   a  S.run_rrt_batch of the B sessions (B contexts)                                     - this build (--a-builds new,parent:
@@ -28,7 +29,8 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "tests"))
 OUT = os.path.join(ROOT, "profiles", "rrt_batch_probe.jsonl")
-KINDS = {"rrt": (1, False), "star": (1, True), "multi": (10, False)}
+KINDS = {"rrt": (1, False, False), "star": (1, True, False), "multi": (10, False, False),   # roots, optimize, lazy_edge
+         "lazy": (1, False, True), "lazy_star": (1, True, True)}
 KEYS = ("iterations", "solved", "n_nodes", "n_live_trees", "merges", "n_links", "collide_calls", "path_free_calls", "nn_queries",
         "rng_draws")
 
@@ -42,6 +44,9 @@ def fingerprint(r):
         h.update(n[k].tobytes())
     for k in sorted(l):
         h.update(l[k].tobytes())
+    if r.lazy_edge:
+        h.update(json.dumps([st["lazy_distance"]]).encode())
+        h.update(r.lazy_plan().tobytes())
     return h.hexdigest()[:16]
 
 
@@ -49,7 +54,7 @@ def child(a):
     import common
     import space_filling_forest_star_amd as S
     sc = common.scenario("dense3d")
-    n_roots, optimize = KINDS[a.kind]
+    n_roots, optimize, lazy = KINDS[a.kind]
     n_ctx = a.B if a.leg == "a" else 1
     ctxs = []
     for _ in range(n_ctx):
@@ -57,11 +62,13 @@ def child(a):
         c.upload_env(sc["env"])
         c.upload_robot(sc["robot"])
         ctxs.append(c)
-    roots = common.free_roots(lambda p: int(ctxs[0].collide_poses(p[None, :])[0]), sc["limits"], 10, seed=1)[:n_roots]
+    roots = common.free_roots(lambda p: int(ctxs[0].collide_poses(p[None, :])[0]), sc["limits"], 10, seed=1)
+    goal = roots[1] if lazy else None
+    roots = roots[:n_roots]
 
     def session(ctx, seed, iters):
         return S.Rrt(ctx, roots, sc["limits"], dist_tree=sc["dist_tree"], sampling_dist=sc["sampling_dist"], dim=6,
-                     max_iterations=iters, wave=0, seed=seed, optimize=optimize)
+                     max_iterations=iters, wave=0, seed=seed, optimize=optimize, goal=goal, lazy_edge=lazy)
 
     stats, fps = [], []
     if a.leg == "a":
@@ -93,7 +100,8 @@ def child(a):
     its = sum(s["iterations"] for s in stats)
     print("RESULT " + json.dumps({
         "leg": a.leg, "build": a.build, "kind": a.kind, "B": a.B, "repeat": a.repeat, "seconds": dt, "mirror_seconds": dt_sync,
-        "iterations": its, "nodes": sum(s["n_nodes"] for s in stats), "iterations_per_s": its / (dt + dt_sync),
+        "iterations": its, "nodes": sum(s["n_nodes"] for s in stats), "solved": sum(s["solved"] for s in stats),
+        "iterations_per_s": its / (dt + dt_sync),
         "launches": max(s.get("batch_launches", 0) for s in stats),
         "batch_host_iterations": sum(s.get("batch_host_iterations", 0) for s in stats), "merges": sum(s["merges"] for s in stats),
         "waves": sum(s["waves"] for s in stats), "fingerprints": fps}), flush=True)
@@ -136,6 +144,9 @@ def main():
             for leg, build, B in legs:
                 env = dict(os.environ)
                 env.pop("SFFGPU_LIB", None)
+                env.pop("SFFGPU_LAZY_BATCH", None)
+                if KINDS[kind][2]:
+                    env["SFFGPU_LAZY_BATCH"] = "1"      # (read when a session is created; a build from before the knob ignores it)
                 if build == "parent":
                     env["SFFGPU_LIB"] = os.path.abspath(a.parent_lib)
                 cmd = [sys.executable, os.path.abspath(__file__), "--child", "--leg", leg, "--build", build, "--kind", kind, "--B", str(B),

@@ -822,7 +822,8 @@ def run_batch(forests, max_waves=0):
 def run_rrt_batch(sessions, max_iterations=0):
     """Advance independent RRT / RRT* / Multi-T-RRT sessions together (sffgpu_rrt_run_batch): one wavefront per session, one
     kernel launch per kind for all of them; each session ends exactly as its own run(max_iterations) with wave=1 would leave
-    it.  Every session lives on a context of its own, all on one device.  An error names the member it came from."""
+    it.  Every session lives on a context of its own, all on one device.  A lazy_edge session is a member only if it was
+    created with SFFGPU_LAZY_BATCH=1 in the environment.  An error names the member it came from."""
     sessions = list(sessions)
     L = lib()
     if not hasattr(L, "sffgpu_rrt_run_batch"):
@@ -842,8 +843,9 @@ def run_rrt_batch(sessions, max_iterations=0):
                 if id(getattr(r, "ctx", None)) in seen and i not in bad:
                     bad.append(i)
                 seen.setdefault(id(getattr(r, "ctx", None)), i)
-            msg += ": not a session batch%s (needs n >= 1 RRT / RRT* sessions, none of them lazy_edge, none of them twice, each on a" \
-                   " context of its own, all on one device)" % ((", member %d" % min(bad)) if bad else "")
+            msg += ": not a session batch%s (needs n >= 1 RRT / RRT* sessions, a lazy_edge one only if it was created under" \
+                   " SFFGPU_LAZY_BATCH=1, none of them twice, each on a context of its own, all on one device)" \
+                   % ((", member %d" % min(bad)) if bad else "")
         raise SffGpuError(msg)
 
 

@@ -313,7 +313,7 @@ int sffgpu_rrt_run(sffgpu_rrt* r, int max_iterations) {
   GUARD(r->owner, r->r->run(max_iterations));
 }
 int sffgpu_rrt_run_batch(sffgpu_rrt* const* r, int n, int max_iterations, int32_t* failed) {
-  return run_batch_entry(r, n, failed, [](const Rrt& m) { return !m.cfg.lazy_edge && m.ctx->grid_on; },
+  return run_batch_entry(r, n, failed, [](const Rrt& m) { return m.batch_eligible(); },
                          [&](Rrt* const* m, int* bad) { run_rrt_batch(m, n, max_iterations, bad); });
 }
 // (a session batch may have left the device block ahead of the host mirror the getters read)

@@ -587,6 +587,7 @@ struct Rrt {
   bool knn_by_grid(const int32_t* tree, int nq, int k) const;
   static constexpr int small_mul = 4;   // a cut wave is followed by small_mul x what survived, up to kn.rrt_small slots
   void expand(int tree_to_expand, unsigned iteration);
+  int pick_tree();                                      // :95; a lazy edge draws none (src/lazy.h:178-182)
   void draw_target(double rnd[6]);
   int merge_or_link(int tree_to_expand, int new_id, int nb, bool edge_free, int fh, int ns, int& i);
   int run_wave(int B);   // speculative wave of up to B iterations; returns how many were committed
@@ -619,6 +620,7 @@ struct Rrt {
     sffk::RrtCtrl last{};
   } bd;
   static constexpr int batch_launch_iters = 8192;   // most iterations of one launch (at most 9 engine words each)
+  bool batch_eligible() const { return (!cfg.lazy_edge || kn.lazy_batch) && ctx->grid_on; }   // (the session's snapshot decides, not the call's environment)
   bool batch_done(int iter0, int max_iters) const;  // nothing left to do for a batch call that began at iteration iter0
   int batch_iter() const { return bd.valid ? bd.last.iter : iter; }
   void batch_upload();                               // host mirror -> device block
@@ -629,10 +631,11 @@ struct Rrt {
   ~Rrt();
 };
 
-// Session batches (rrt_batch.cpp; the lock step: batch_lockstep.h): n independent RRT / RRT* / Multi-T-RRT sessions, each on a context of its own, advanced in
-// lock step - one wavefront per session, one launch of k_rrt_seq_batch per kind (RRT / RRT*) for all of them - until each is
-// solved, has run Problem::maxIterations or max_iterations more iterations (0 = no bound).  The caller has checked the
-// members (no lazy_edge, distinct contexts, one device).  A member that throws ends the call: *failed = its index, the
+// Session batches (rrt_batch.cpp; the lock step: batch_lockstep.h): n independent RRT / RRT* / Multi-T-RRT sessions and lazy
+// edges, each on a context of its own, advanced in lock step - one wavefront per session, one launch of k_rrt_seq_batch per
+// kind (RRT / RRT* / lazy RRT / lazy RRT*) for all of them - until each is solved, has run Problem::maxIterations or
+// max_iterations more iterations (0 = no bound).  The caller has checked the members (Rrt::batch_eligible: a lazy_edge
+// session only when it was created under SFFGPU_LAZY_BATCH=1; distinct contexts, one device).  A member that throws ends the call: *failed = its index, the
 // exception goes on to the caller; every other member has been taken in after a whole number of launches.
 void run_rrt_batch(Rrt* const* members, int n, int max_iterations, int* failed);
 

@@ -700,16 +700,20 @@ void launch_spec_waves(hipStream_t s, const SpecArgs& a);
 // wavefront = the one-by-one loop of members_dev[b] (src/rrt.h:93-99 + expandNode :128-322) in the reference's order, every
 // edge checked only when the loop reaches it.  What the loop cannot settle exactly it leaves to the host: the iteration is
 // rolled back to its start (nothing of it was written) and the launch returns with SFFK_RRT_HOST_ITER.
+// A lazy edge (LazyTSP::runRRT, src/lazy.h:160-284: one tree, no tree pick, k from size + 1) is a kind of its own: the LAZY
+// instances, whose loop ends with SFFK_RRT_SOLVED when a new node comes within treeDistance of the goal.
 struct RrtCtrl {                     // control / status block of one session (HBM; copied back after every launch)
   int32_t n_nodes, iter;             // nodes in the store, iterations run (Rrt::iter)
   int32_t status, reason;            // SFFK_RRT_* below
-  int32_t grid_ovf, pad0;            // the grid's overflow counter when the launch ended
+  int32_t grid_ovf, lazy_last;       // the grid's overflow counter when the launch ended; SFFK_RRT_SOLVED: the node that reached the goal
   unsigned long long cursor;         // engine words consumed so far (absolute: Mt64::draws)
   unsigned long long collide_calls, path_free_calls, nn_queries;   // reference-equivalent counters
+  double lazy_distance;              // SFFK_RRT_SOLVED: distance(goal, that node) + its cost (src/lazy.h:268); only the LAZY instances write the two
 };
 #define SFFK_RRT_RAN 0               // the launch ended normally: its iterations, the session's budget or the engine words ran out
 #define SFFK_RRT_HOST_ITER 1         // the next iteration is the host's (Rrt::expand): reason says why
 #define SFFK_RRT_GRID 2              // the grid's overflow list wants the grid re-celled
+#define SFFK_RRT_SOLVED 3            // a lazy edge reached its goal in the launch's last iteration: the session is over
 #define SFFK_RRT_WHY_LINK 1          // a free edge to another live tree: link + merge (src/rrt.h:233-316)
 #define SFFK_RRT_WHY_TIE 2           // two nodes at exactly one distance in a tree whose list is not in id order
 #define SFFK_RRT_WHY_CAPACITY 3      // node arrays, k beyond the lanes' list, more live trees than lanes
@@ -733,9 +737,10 @@ struct RrtSeqArgs {
   int merged;                         // a tree has eaten another: its list is no longer in id order
   int grid_ovf_limit;
 };
-// All members of a launch are of one kind (optimize: RRT*), lds = the largest collide_lds_bytes(rob.n_tri, 1) among them.
-// Returns the first error of setting the kernel's attribute or of the launch itself.
-hipError_t launch_rrt_seq_batch(hipStream_t s, const RrtSeqArgs* members_dev, int n, bool optimize, size_t lds);
+// All members of a launch are of one kind (optimize: RRT*; lazy: lazy edges, every member with one live tree), lds = the
+// largest collide_lds_bytes(rob.n_tri, 1) among them.  Returns the first error of setting the kernel's attribute or of the
+// launch itself.
+hipError_t launch_rrt_seq_batch(hipStream_t s, const RrtSeqArgs* members_dev, int n, bool optimize, bool lazy, size_t lds);
 // the transcendental values of n engine words (3 doubles per word: cos, sin of the word as an angle, acos of it as the pitch draw)
 void launch_ring_trig(hipStream_t s, const uint64_t* words, double* trig, int n);
 // multi-GPU: the answer record of one sample as it travels in the all-gather of a round:

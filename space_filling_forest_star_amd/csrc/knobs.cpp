@@ -99,6 +99,7 @@ Knobs Knobs::from_env() {
   k.rrt_grow = int_in("SFFGPU_RRT_GROW", k.rrt_grow, 100);
   k.rrt_no_grid = is_set("SFFGPU_RRT_NO_GRID");
   k.rrt_no_chain_conn = is_set("SFFGPU_RRT_NO_CHAIN_CONN");
+  k.lazy_batch = flag("SFFGPU_LAZY_BATCH", k.lazy_batch);
   return k;
 }
 

@@ -90,6 +90,8 @@ struct Knobs {
   int rrt_grow = 150;               // SFFGPU_RRT_GROW (>= 100): ... or by this percentage of what survived (+ 1)
   bool rrt_no_grid = false;         // SFFGPU_RRT_NO_GRID (set at all): k-nearest by linear sweep
   bool rrt_no_chain_conn = false;   // SFFGPU_RRT_NO_CHAIN_CONN (set at all): Multi-T-RRT, the other trees' query as a call of its own
+  bool lazy_batch = false;          // SFFGPU_LAZY_BATCH=1: a lazy_edge session (LazyTSP::runRRT, src/lazy.h:160-284) may be a member of a session batch
+                                    // (k_rrt_seq_batch<., true>); 0 = a batch refuses it
 
   static Knobs from_env();
 };

@@ -130,6 +130,11 @@ void Rrt::knn(const double* q, int nq, const int32_t* tree, int k, std::vector<s
 
 static uint64_t seg_calls(int fh, int ns) { return fh > 0 ? (uint64_t)fh : (uint64_t)ns; }
 
+// the iteration's tree to expand: uniform_int(0, numTrees) over the live-tree list (src/rrt.h:95); a lazy edge has one tree
+// and draws none (src/lazy.h:178-182).  The one-by-one loop, the speculative wave and the iteration a session batch hands
+// over all come through here, so none of them can consume a word the others do not
+int Rrt::pick_tree() { return cfg.lazy_edge ? 0 : tree_frontier[rng.uniform_int(0, num_trees)]; }
+
 // the iteration's steering target: the goal with probability priorityBias (:130-131), else
 // RandGen::randomPointInSpace (src/randGen.h:124-146); Y is drawn before X (g++ evaluates the two arguments
 // of point.set(...) right to left — pinned by tests/golden/ref_primitives.json)
@@ -341,7 +346,7 @@ int Rrt::run_wave(int B) {
   for (int j = 0; j < B; ++j) {
     w[j].draws_before = rng.draws;
     w[j].slot = j;
-    w[j].tree = cfg.lazy_edge ? 0 : tree_frontier[rng.uniform_int(0, num_trees)];   // (src/lazy.h:181 draws no tree)
+    w[j].tree = pick_tree();
     draw_target(w[j].rnd);
   }
   const uint64_t draws_end = rng.draws;
@@ -926,8 +931,7 @@ void Rrt::run(int max_iters) {
     if (cfg.wave == 1) {
       ++done;
       ++iter;
-      int tree = cfg.lazy_edge ? 0 : tree_frontier[rng.uniform_int(0, num_trees)];   // :95
-      expand(tree, (unsigned)iter);
+      expand(pick_tree(), (unsigned)iter);
       continue;
     }
     // wave size: fixed by the caller, or adapted to how much of the last wave survived

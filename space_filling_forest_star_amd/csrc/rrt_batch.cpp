@@ -8,7 +8,8 @@
 //   - a member is live while it has iterations to run; an iteration the kernel handed over (link + merge, an exact tie in a
 //     merged tree's list, a capacity) runs alone through Rrt::expand first and the device block is uploaded again;
 //   - its engine words come from the block's own copy of the generator;
-//   - two kinds (RRT, RRT*: the template instances of the kernel), at most batch_launch_iters iterations a launch;
+//   - four kinds (RRT, RRT*, lazy RRT, lazy RRT*: the template instances of the kernel), at most batch_launch_iters iterations
+//     a launch; a lazy edge (created under SFFGPU_LAZY_BATCH=1) that reaches its goal comes back solved and takes no further part;
 //   - a member is taken in: node count of the store, the grid re-celled when its overflow list asks for it.
 // The host mirror (nodes, tree lists, counters, the Mt64) is refreshed lazily (batch_sync_host): by the getters, by
 // sffgpu_rrt_run and by the host iteration.
@@ -209,6 +210,11 @@ void Rrt::batch_take_in() {
   ++st.batch_launches;
   c.store_n = d.last.n_nodes;        // (the kernel wrote store and grid itself)
   c.grid_inserted = d.last.n_nodes;
+  if (d.last.status == SFFK_RRT_SOLVED) {   // a lazy edge reached its goal (Rrt::lazy_goal_check, on the device): the member is done
+    solved = true;
+    lazy_last = d.last.lazy_last;
+    lazy_distance = d.last.lazy_distance;
+  }
   if (d.last.status == SFFK_RRT_GRID || d.last.grid_ovf > c.grid_rebuild_at()) {
     if (d.last.grid_ovf > c.gridv.ovf_cap) throw HipError{"rrt batch: neighbour grid overflow list exhausted during a launch (nodes were dropped)"};
     HIPCHK(hipSetDevice(c.device));
@@ -222,15 +228,14 @@ void Rrt::batch_host_iteration() {
   batch_sync_host();
   bd.valid = false;
   ++iter;
-  const int tree = tree_frontier[rng.uniform_int(0, num_trees)];                 // :95
-  expand(tree, (unsigned)iter);
+  expand(pick_tree(), (unsigned)iter);   // (a lazy edge: no word for the tree, and expand ends with lazy_goal_check)
   ++st.batch_host_iterations;
 }
 
 namespace {
 struct RrtFamily {
   using Args = sffk::RrtSeqArgs;
-  static constexpr int n_kinds = 2;   // RRT, RRT*
+  static constexpr int n_kinds = 4;   // RRT, RRT*, lazy RRT, lazy RRT*
   Rrt* const* m;
   int n, max_iterations;
   std::vector<int> iter0;
@@ -257,10 +262,10 @@ struct RrtFamily {
   void ring_append(int i, const uint64_t* w, size_t nw) { m[i]->bd.wr.append(m[i]->ctx->copy_stream, w, nullptr, nw); }
   WordRing& ring(int i) { return m[i]->bd.wr; }
   Args prepare(int i, int iters) { return m[i]->batch_prepare(iters); }
-  int kind(int i) { return m[i]->cfg.optimize ? 1 : 0; }
+  int kind(int i) { return (m[i]->cfg.lazy_edge ? 2 : 0) + (m[i]->cfg.optimize ? 1 : 0); }
   hipStream_t stream(int i) { return m[i]->ctx->stream; }
   StatusBlock status(int i) { return {m[i]->bd.h_ctrl.p, m[i]->bd.ctrl.p, sizeof(sffk::RrtCtrl)}; }
-  hipError_t launch(hipStream_t s, const Args* a, int count, int kind, size_t lds) { return sffk::launch_rrt_seq_batch(s, a, count, kind != 0, lds); }
+  hipError_t launch(hipStream_t s, const Args* a, int count, int kind, size_t lds) { return sffk::launch_rrt_seq_batch(s, a, count, (kind & 1) != 0, (kind & 2) != 0, lds); }
   void take_in(int i, double*) { m[i]->batch_take_in(); }
   void finish(double wall, double) { for (int i = 0; i < n; ++i) m[i]->st.total_ms += wall; }
 };

@@ -52,7 +52,11 @@ __device__ __attribute__((noinline)) void rrt_knn_sweep(const NodeStoreMut& st, 
   }
 }
 
-template <bool OPT>
+// LAZY: the member is a lazy edge, LazyTSP::runRRT (src/lazy.h:160-284) - ONE tree from one root, so no tree is drawn (:178-182)
+// and nothing of the other-trees step exists; k = (size_t)(2e log10(size + 1)) (:204); the new node within treeDistance of the
+// goal ends the edge's search (:262-276, no edge check towards the goal): status SFFK_RRT_SOLVED.  All of it sits behind the
+// template parameter - the other two instances are the code they were.
+template <bool OPT, bool LAZY>
 __device__ __forceinline__ void rrt_seq_body(const RrtSeqArgs& A) {
   extern __shared__ double lds_d[];
   __shared__ int32_t s_fh, s_ovf;
@@ -73,6 +77,10 @@ __device__ __forceinline__ void rrt_seq_body(const RrtSeqArgs& A) {
   unsigned long long cursor = c->cursor, cc = c->collide_calls, pf = c->path_free_calls, nq = c->nn_queries;
   unsigned long long ex_smp = 0;
   int status = SFFK_RRT_RAN, reason = 0;
+  int lazy_last = -1;              // (LAZY) the node that reached the goal
+  double lazy_distance = 0;        // (LAZY) distance(goal, that node) + the node's cost: the length of the edge (src/lazy.h:268)
+  // (a lazy edge has one tree and never merges: what exists for a tree that has eaten another is dead in its instances)
+  auto merged = [&]() { if constexpr (LAZY) return false; else return A.merged != 0; };
   const int n_live = A.n_live;
   // lane i speaks for the i-th live tree (frontier order) in the other-trees step
   const int my_live = lane < n_live ? A.live[lane] : -1;
@@ -98,15 +106,21 @@ __device__ __forceinline__ void rrt_seq_body(const RrtSeqArgs& A) {
     const int iter_a = iter;
     auto hand_over = [&](int why) { cursor = cur_a; cc = cc_a; pf = pf_a; nq = nq_a; iter = iter_a; status = SFFK_RRT_HOST_ITER; reason = why; };
     // ---- 1. the tree to expand (:95): uniform_int(0, numTrees) over the live-tree list, a rejected word draws again
-    int pick;
-    do { pick = lemire_pick(A.ring[cursor & A.ring_mask], (unsigned long long)A.pick_range); ++cursor; } while (pick < 0 && cursor < A.words_end);
-    if (pick < 0) { cursor = cur_a; break; }
+    // (LAZY: the one tree, no engine word - src/lazy.h:178-182)
+    int pick = 0;
+    if constexpr (!LAZY) {
+      do { pick = lemire_pick(A.ring[cursor & A.ring_mask], (unsigned long long)A.pick_range); ++cursor; } while (pick < 0 && cursor < A.words_end);
+      if (pick < 0) { cursor = cur_a; break; }
+    }
     ++iter;
     const int mine = A.live[pick];
     // ---- 2. the steering target (:130-134): the goal with probability priorityBias, else randomPointInSpace (Y before X)
+    // (LAZY: no goal bias, no word for it)
     double rnd[6];
     bool to_goal = false;
-    if (A.priority_bias != 0) { to_goal = uniform_real(A.ring[cursor & A.ring_mask], 0.0, 1.0) <= A.priority_bias; ++cursor; }
+    if constexpr (!LAZY) {
+      if (A.priority_bias != 0) { to_goal = uniform_real(A.ring[cursor & A.ring_mask], 0.0, 1.0) <= A.priority_bias; ++cursor; }
+    }
     if (to_goal) {
       for (int k = 0; k < 6; ++k) rnd[k] = A.goal[k];
     } else {
@@ -128,9 +142,11 @@ __device__ __forceinline__ void rrt_seq_body(const RrtSeqArgs& A) {
     nq += 1;
     TopK nt{1.0e300, 0x7fffffff};
     int n_near = 0;
-    knn(rnd, mine, A.merged ? 2 : 1, nt, n_near);
+    knn(rnd, mine, merged() ? 2 : 1, nt, n_near);
     if (n_near < 1) { hand_over(SFFK_RRT_WHY_CAPACITY); break; }                  // (a live tree always holds its root)
-    if (n_near >= 2 && __shfl(nt.d, 0) == __shfl(nt.d, 1)) { hand_over(SFFK_RRT_WHY_TIE); break; }
+    if constexpr (!LAZY) {
+      if (n_near >= 2 && __shfl(nt.d, 0) == __shfl(nt.d, 1)) { hand_over(SFFK_RRT_WHY_TIE); break; }
+    }
     int nearest = __shfl(nt.id, 0);
     double cpos[6], qp[6];
     for (int k = 0; k < 6; ++k) cpos[k] = sq_f64(A.st.pos + 6 * (size_t)nearest + k);
@@ -154,7 +170,7 @@ __device__ __forceinline__ void rrt_seq_body(const RrtSeqArgs& A) {
     if (!(sq_edge_clear_fast(A.env, cpos, qp, lane, cc, ex_smp) || sq_path_free(A.env, A.rob, rtri, stack, cand, queue, stage, cpos, qp, &s_fh, &s_ovf, lane, cc, ex_smp, flt))) continue;
     // ---- 8. the other live trees (:219-319), ahead of choose-parent / append / rewire (see above): per tree its nearest node,
     // which only matters inside treeDistance - every node of another tree in that ball, from the cells its box touches
-    if (n_live > 1) {
+    if constexpr (!LAZY) if (n_live > 1) {
       nq += (unsigned long long)(n_live - 1);
       const double r = A.dist_tree;
       const double ri = (r + A.sweep_abs_eps) * (1.0 + 1e-5);
@@ -230,7 +246,7 @@ __device__ __forceinline__ void rrt_seq_body(const RrtSeqArgs& A) {
       while (todo && !why) {
         const int src_lane = __ffsll((long long)todo) - 1;
         todo &= todo - 1;
-        if (A.merged && __shfl((int)btie, src_lane)) { why = SFFK_RRT_WHY_TIE; break; }
+        if (merged() && __shfl((int)btie, src_lane)) { why = SFFK_RRT_WHY_TIE; break; }
         const int nb = __shfl(bid, src_lane);
         double np6[6];
         for (int k = 0; k < 6; ++k) np6[k] = sq_f64(A.st.pos + 6 * (size_t)nb + k);
@@ -249,12 +265,13 @@ __device__ __forceinline__ void rrt_seq_body(const RrtSeqArgs& A) {
     if (OPT) {
       dcl_new = dist6(qp, cpos);
       best = dcl_new + sq_f64(A.d_root + nearest);
-      const int k = __popcll(__ballot(lane > 0 && lane <= SFFK_STAR_KMAX + 1 && A.ktab[lane] <= n_nodes));   // (size_t)(2e log10 N), :160
+      // (size_t)(2e log10 N), :160; LAZY: N = size + 1 (src/lazy.h:204) - k is 1 when only the root exists
+      const int k = __popcll(__ballot(lane > 0 && lane <= SFFK_STAR_KMAX + 1 && A.ktab[lane] <= n_nodes + (LAZY ? 1 : 0)));
       if (k > SFFK_STAR_KMAX) { hand_over(SFFK_RRT_WHY_CAPACITY); break; }
       nq += 1;                                                                              // :166 knnSearch
       if (k > 0) {
-        knn(qp, mine, A.merged ? k + 1 : k, mt, n_mem);
-        if (A.merged) {
+        knn(qp, mine, merged() ? k + 1 : k, mt, n_mem);
+        if (merged()) {
           // (the list with one entry more: a tie inside it or at its boundary is the host's)
           const double dn = __shfl_down(mt.d, 1);
           if (__any(lane + 1 < n_mem && mt.d == dn)) { hand_over(SFFK_RRT_WHY_TIE); break; }
@@ -317,12 +334,18 @@ __device__ __forceinline__ void rrt_seq_body(const RrtSeqArgs& A) {
       }
       sq_drain();
     }
+    if constexpr (LAZY) {
+      // ---- the goal test (src/lazy.h:262-276), behind the rewires as in the reference (none of them touches the new node's cost)
+      const double gd = dist6(A.goal, qp);
+      if (gd < A.dist_tree) { status = SFFK_RRT_SOLVED; lazy_last = idn; lazy_distance = gd + best; break; }
+    }
   }
   if (lane == 0) {
     c->n_nodes = n_nodes; c->iter = iter;
     c->status = status; c->reason = reason;
     c->grid_ovf = sq_i32(g.ovf_cnt);
     c->cursor = cursor; c->collide_calls = cc; c->path_free_calls = pf; c->nn_queries = nq;
+    if constexpr (LAZY) { c->lazy_last = lazy_last; c->lazy_distance = lazy_distance; }
   }
 }
 
@@ -330,18 +353,21 @@ __device__ __forceinline__ void rrt_seq_body(const RrtSeqArgs& A) {
 // ring and a control block of its own.  The member's arguments are read through the uniform pointer (scalar registers, like
 // k_seq_waves_batch's); no workgroup ever waits for another one, so any grid size runs - what is not resident at once runs when a
 // slot frees up.
-template <bool OPT>
+template <bool OPT, bool LAZY>
 __global__ __launch_bounds__(64) void k_rrt_seq_batch(const RrtSeqArgs* __restrict__ members, int n) {
   if ((int)blockIdx.x >= n) return;
-  rrt_seq_body<OPT>(members[blockIdx.x]);
+  rrt_seq_body<OPT, LAZY>(members[blockIdx.x]);
 }
 
-hipError_t launch_rrt_seq_batch(hipStream_t s, const RrtSeqArgs* members_dev, int n, bool optimize, size_t lds) {
-  if (n <= 0) return hipSuccess;
-  const void* fn = optimize ? reinterpret_cast<const void*>(k_rrt_seq_batch<true>) : reinterpret_cast<const void*>(k_rrt_seq_batch<false>);
-  const hipError_t e = set_dyn_lds(fn, lds, 48 * 1024);
+template <bool OPT, bool LAZY>
+static hipError_t launch_rrt_seq_batch_as(hipStream_t s, const RrtSeqArgs* members_dev, int n, size_t lds) {
+  const hipError_t e = set_dyn_lds(k_rrt_seq_batch<OPT, LAZY>, lds, 48 * 1024);
   if (e != hipSuccess) return e;
-  if (optimize) hipLaunchKernelGGL(k_rrt_seq_batch<true>, dim3(n), dim3(64), lds, s, members_dev, n);
-  else hipLaunchKernelGGL(k_rrt_seq_batch<false>, dim3(n), dim3(64), lds, s, members_dev, n);
+  hipLaunchKernelGGL((k_rrt_seq_batch<OPT, LAZY>), dim3(n), dim3(64), lds, s, members_dev, n);
   return hipGetLastError();
+}
+hipError_t launch_rrt_seq_batch(hipStream_t s, const RrtSeqArgs* members_dev, int n, bool optimize, bool lazy, size_t lds) {
+  if (n <= 0) return hipSuccess;
+  if (lazy) return optimize ? launch_rrt_seq_batch_as<true, true>(s, members_dev, n, lds) : launch_rrt_seq_batch_as<false, true>(s, members_dev, n, lds);
+  return optimize ? launch_rrt_seq_batch_as<true, false>(s, members_dev, n, lds) : launch_rrt_seq_batch_as<false, false>(s, members_dev, n, lds);
 }
