@@ -37,6 +37,13 @@ const char* sffgpu_last_error(sffgpu_ctx* ctx); /* ctx may be NULL: last create(
  * src/environment.h:306-316).  The ENV model may be empty (HasMap == false). */
 int sffgpu_mesh_upload(sffgpu_ctx* ctx, int role, const double* tri9, int n_tri);
 
+/* Poses.  Wherever the caller hands in poses (x y z yaw pitch roll) - sffgpu_collide_poses, sffgpu_collide_segments, the
+ * centres of sffgpu_sample_steer, the roots and the goal of sffgpu_forest_create / sffgpu_rrt_create - every coordinate
+ * must be finite and every angle must lie within +-2^20 * pi/2 (about 1.647e6; SFFP_TRIG_DOMAIN of csrc/sff_pmath.h),
+ * the range over which the library's sine and cosine are accurate to 1 ulp.  Angles need not be normalised to [-pi, pi).
+ * A row outside this is refused with SFFGPU_ERR_ARG before anything is launched; sffgpu_last_error names the argument
+ * and the row. */
+
 /* Environment::Collide(position) (src/environment.h:306-316 -> RAPID_Collide :268-276):
  * hit[i] = 1 if the robot posed at pos6[i] = (x y z yaw pitch roll) touches any ENV triangle. */
 int sffgpu_collide_poses(sffgpu_ctx* ctx, const double* pos6, int n, uint8_t* hit);

@@ -1,11 +1,13 @@
 // capi.cpp — extern "C" surface of libsffgpu.so (declared in include/sffgpu.h).
 #include <algorithm>
+#include <cstdio>
 #include <cstdlib>
 #include <cstring>
 #include <string>
 #include <vector>
 
 #include "engine.h"
+#include "sff_pmath.h"
 
 namespace sff { void forest_profile_dump(); }
 using namespace sff;
@@ -35,6 +37,26 @@ static std::string g_create_err;
     (ctxp)->c->err = e.what();                     \
     return SFFGPU_ERR_STATE;                       \
   }
+
+// Poses from the caller (include/sffgpu.h, "Poses"): every coordinate finite, every angle within the domain of the
+// portable trig's reduction.  Checked on the host before anything is launched; the message names the argument and the row.
+static bool poses_ok(sffgpu_ctx* ctx, const char* fn, const char* arg, const double* p6, int n) {
+  for (int i = 0; i < n; ++i)
+    for (int j = 0; j < 6; ++j) {
+      const double v = p6[6 * (size_t)i + j];
+      const bool finite = v - v == 0.0;
+      if (finite && (j < 3 || (v <= SFFP_TRIG_DOMAIN && v >= -SFFP_TRIG_DOMAIN))) continue;
+      char msg[200];
+      if (!finite)
+        snprintf(msg, sizeof msg, "%s: %s row %d: coordinate %d is not finite", fn, arg, i, j);
+      else
+        snprintf(msg, sizeof msg, "%s: %s row %d: angle %g (coordinate %d) is outside +-%.17g", fn, arg, i, v, j,
+                 (double)SFFP_TRIG_DOMAIN);
+      ctx->c->err = msg;
+      return false;
+    }
+  return true;
+}
 
 static Forest* engine_of(sffgpu_forest* h) { return h->f; }
 static Rrt* engine_of(sffgpu_rrt* h) { return h->r; }
@@ -108,6 +130,7 @@ int sffgpu_mesh_upload(sffgpu_ctx* ctx, int role, const double* tri9, int n_tri)
 
 int sffgpu_collide_poses(sffgpu_ctx* ctx, const double* pos6, int n, uint8_t* hit) {
   if (!ctx || n < 0 || (n > 0 && (!pos6 || !hit))) return SFFGPU_ERR_ARG;
+  if (!poses_ok(ctx, "sffgpu_collide_poses", "pos6", pos6, n)) return SFFGPU_ERR_ARG;
   GUARD(ctx, ctx->c->collide_poses(pos6, n, hit));
 }
 
@@ -119,6 +142,8 @@ int sffgpu_collide_transforms(sffgpu_ctx* ctx, const double* rt12, int n, uint8_
 int sffgpu_collide_segments(sffgpu_ctx* ctx, const double* a6, const double* b6, int n, uint8_t* is_free,
                             int32_t* first_hit, int32_t* n_samples) {
   if (!ctx || n < 0 || (n > 0 && (!a6 || !b6 || !is_free))) return SFFGPU_ERR_ARG;
+  if (!poses_ok(ctx, "sffgpu_collide_segments", "a6", a6, n) || !poses_ok(ctx, "sffgpu_collide_segments", "b6", b6, n))
+    return SFFGPU_ERR_ARG;
   GUARD(ctx, ctx->c->collide_segments(a6, b6, n, is_free, first_hit, n_samples));
 }
 
@@ -126,6 +151,7 @@ int sffgpu_sample_steer(sffgpu_ctx* ctx, const uint64_t* words, const double* ce
                         const double limits[6], double* out6, uint8_t* in_limits) {
   if (!ctx || n < 0 || (dim != 2 && dim != 6) || (n > 0 && (!words || !center6 || !limits || !out6 || !in_limits)))
     return SFFGPU_ERR_ARG;
+  if (!poses_ok(ctx, "sffgpu_sample_steer", "center6", center6, n)) return SFFGPU_ERR_ARG;
   GUARD(ctx, ctx->c->sample_steer(words, center6, n, dist, dim, limits, out6, in_limits));
 }
 
@@ -172,6 +198,8 @@ int sffgpu_forest_create(sffgpu_ctx* ctx, const sffgpu_forest_cfg* cfg, const do
                          sffgpu_forest** out) {
   if (!ctx || !cfg || !roots6 || n_roots <= 0 || !out) return SFFGPU_ERR_ARG;
   *out = nullptr;
+  if (!poses_ok(ctx, "sffgpu_forest_create", "roots6", roots6, n_roots)) return SFFGPU_ERR_ARG;
+  if (cfg->has_goal && !poses_ok(ctx, "sffgpu_forest_create", "cfg->goal", cfg->goal, 1)) return SFFGPU_ERR_ARG;
   GUARD(ctx, {
     Forest* F = new Forest(ctx->c, *cfg, roots6, n_roots);
     sffgpu_forest* h = new sffgpu_forest;
@@ -295,6 +323,8 @@ int sffgpu_forest_path_plan(sffgpu_forest* f, int i, int j, int32_t* node_ids, i
 int sffgpu_rrt_create(sffgpu_ctx* ctx, const sffgpu_rrt_cfg* cfg, const double* roots6, int n_roots, sffgpu_rrt** out) {
   if (!ctx || !cfg || !roots6 || n_roots <= 0 || !out) return SFFGPU_ERR_ARG;
   *out = nullptr;
+  if (!poses_ok(ctx, "sffgpu_rrt_create", "roots6", roots6, n_roots)) return SFFGPU_ERR_ARG;
+  if ((cfg->has_goal || cfg->lazy_edge) && !poses_ok(ctx, "sffgpu_rrt_create", "cfg->goal", cfg->goal, 1)) return SFFGPU_ERR_ARG;
   GUARD(ctx, {
     Rrt* R = new Rrt(ctx->c, *cfg, roots6, n_roots);
     sffgpu_rrt* h = new sffgpu_rrt;

@@ -7,8 +7,15 @@
 // routines are therefore written once, with only IEEE-754 +,-,*,/ and sqrt, and are
 // compiled with -ffp-contract=off for BOTH the gfx950 kernels and the host, so the
 // HIP path and the CPU checker produce identical bits.  Algorithms: Cody–Waite
-// three-part pi/2 reduction and the classic (Sun fdlibm-lineage) minimax kernels;
-// accuracy < 1 ulp, verified against glibc in tests/test_pmath.py.
+// three-part pi/2 reduction and the classic (Sun fdlibm-lineage) minimax kernels.
+//
+// Accuracy: every result is less than 1 ulp from the exact value for |x| <= SFFP_TRIG_DOMAIN
+// (psin, pcos) and on [-1, 1] (pacos).  tests/test_pmath.py holds the host build to that
+// against 200-bit arithmetic on the arguments where this file branches (quadrant boundaries,
+// the pi/4 literal, pacos's 0.5 / 2^-57 / 1 thresholds, the domain's edge), and to "never more
+// than 1 ulp from glibc" as a second statement; the measured worst errors are in DESIGN.md
+// section 6.  tests/test_gpu_trig_edges.py holds the gfx950 build to the host build's bits on
+// the same arguments.  Both sides compile this one file, so no other test can see an error in it.
 #pragma once
 #include <string.h>
 
@@ -50,7 +57,13 @@ SFF_HD double kernel_cos(double x, double y) {
   return w + (((1.0 - w) - hz) + (z * r - x * y));
 }
 
-// x = k*pi/2 + (y0 + y1), |y0| <= pi/4 (+ a hair).  Valid for |x| < ~1e6.
+// The reduction below is exact while k*P1 and k*P2 are exact products.  P1 and P2 carry 33
+// significant bits, so that holds for |k| <= 2^20: |x| <= 2^20 * pi/2 ~ 1.647e6.  Beyond it the
+// result degrades quickly (7 digits at 1e9) and a non-finite x reaches (int)k: the C ABI refuses
+// such angles (capi.cpp) instead.
+#define SFFP_TRIG_DOMAIN (1048576.0 * 1.57079632679489661923)
+
+// x = k*pi/2 + (y0 + y1), |y0| <= pi/4 (+ a hair).  Valid for |x| <= SFFP_TRIG_DOMAIN.
 SFF_HD int rem_pio2(double x, double* y0, double* y1) {
   const double INVPIO2 = 6.36619772367581382433e-01;   // 2/pi
   const double P1 = 1.57079632673412561417e+00;        // first 33 bits of pi/2
@@ -72,6 +85,7 @@ SFF_HD int rem_pio2(double x, double* y0, double* y1) {
 
 SFF_HD double psin(double x) {
   double ax = x < 0 ? -x : x;
+  if (x == 0.0) return x;  // keeps the sign of -0.0: the kernel's x + (+0) would lose it
   if (ax <= 0.78539816339744827900) return kernel_sin(x, 0.0, 0);
   double y0, y1;
   int n = rem_pio2(x, &y0, &y1) & 3;

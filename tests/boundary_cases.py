@@ -181,7 +181,7 @@ def coarse_lattice(n, pitch, offset):
     return g * pitch + offset
 
 
-def tangent_world(robot, n, seed, gap, offset, rotation, shape="tip"):
+def tangent_world(robot, n, seed, gap, offset, rotation, shape="tip", angles=None):
     """n poses and n environment triangles: pose i's robot touches triangle i in exactly one point when gap == 0.
 
     The point is the world position of the robot's farthest vertex (from the centre of its bounding sphere, so the whole
@@ -190,12 +190,15 @@ def tangent_world(robot, n, seed, gap, offset, rotation, shape="tip"):
     gap > 0 moves the triangle outward by gap * max(radius, |offset|): a strict gap, of the order of `gap` relative to
     the coordinates in play.  Poses sit on a lattice of pitch 40 radii (a pose can only touch its own triangle), angles
     are uniform in [-pi, pi).  shape "tip": the triangle stands on the sphere's tangent plane with one vertex (its own
-    plane cuts the sphere); "flat": it lies in the tangent plane.  Returns (poses n x 6, env n x 9)."""
+    plane cuts the sphere); "flat": it lies in the tangent plane.  angles: an n x 3 array (yaw pitch roll) used instead
+    of the uniform draw.  Returns (poses n x 6, env n x 9)."""
     rc, vfar, radius = robot_sphere(robot)
     rs = np.random.RandomState(seed)
     poses = np.zeros((n, 6))
     poses[:, :3] = coarse_lattice(n, 40.0 * radius, float(offset))
     poses[:, 3:] = rs.uniform(-np.pi, np.pi, (n, 3))
+    if angles is not None:
+        poses[:, 3:] = np.asarray(angles, dtype=np.float64).reshape(n, 3)
     scale = max(radius, abs(float(offset)))
     env = np.zeros((n, 9))
     for i in range(n):

@@ -182,3 +182,104 @@ def test_clearance_bits_never_change_an_answer(S, monkeypatch, name, mode):
     far[:, :3] += 1e4
     assert not ctx.collide_poses(far).any()
     ctx.close()
+
+
+# ------------------------------------------------------------------------------------------------ poses outside the domain
+# include/sffgpu.h, "Poses": a non-finite coordinate, or an angle beyond +-2^20 * pi/2 (SFFP_TRIG_DOMAIN of csrc/sff_pmath.h,
+# where the portable sine / cosine stop being accurate), is refused with SFFGPU_ERR_ARG before anything is launched.
+TRIG_DOMAIN = 2.0 ** 20 * (np.pi / 2)
+
+
+def _call_poses(S, ctx, sc, rows):
+    return ctx.collide_poses(rows)
+
+
+def _other_end(rows):
+    """the same poses one unit along x (an angle at the bound on both ends: a short edge, not 1e7 samples), the entries
+    under test replaced by zeros so that only the argument in question can be refused"""
+    o = rows.copy()
+    o[~np.isfinite(o)] = 0.0
+    o[:, 3:][np.abs(o[:, 3:]) > TRIG_DOMAIN] = 0.0
+    o[:, 0] += 1.0
+    return o
+
+
+def _call_segments_a(S, ctx, sc, rows):
+    return ctx.collide_segments(rows, _other_end(rows))
+
+
+def _call_segments_b(S, ctx, sc, rows):
+    return ctx.collide_segments(_other_end(rows), rows)
+
+
+def _call_sample_steer(S, ctx, sc, rows):
+    words = np.random.RandomState(1).randint(0, 2 ** 62, size=(len(rows), 6)).astype(np.uint64)
+    return ctx.sample_steer(words, rows, sc["sampling_dist"], 6, sc["limits"])
+
+
+def _session(S, kind, ctx, sc, roots, goal):
+    kw = dict(dist_tree=sc["dist_tree"], sampling_dist=sc["sampling_dist"], dim=6, max_iterations=50, seed=3, goal=goal)
+    s = S.Forest(ctx, roots, sc["limits"], wave=16, **kw) if kind == "forest" else S.Rrt(ctx, roots, sc["limits"], **kw)
+    s.run()
+    n = s.stats()["n_nodes"]
+    s.close()
+    return n
+
+
+def _call_forest_roots(S, ctx, sc, rows):
+    return _session(S, "forest", ctx, sc, rows, None)
+
+
+def _call_forest_goal(S, ctx, sc, rows):
+    return _session(S, "forest", ctx, sc, sc["xml_points"][:2], rows[-1])
+
+
+def _call_rrt_roots(S, ctx, sc, rows):
+    return _session(S, "rrt", ctx, sc, rows, None)
+
+
+def _call_rrt_goal(S, ctx, sc, rows):
+    return _session(S, "rrt", ctx, sc, sc["xml_points"][:2], rows[-1])
+
+
+POSE_ENTRY_POINTS = [("sffgpu_collide_poses", "pos6", _call_poses), ("sffgpu_collide_segments", "a6", _call_segments_a),
+                     ("sffgpu_collide_segments", "b6", _call_segments_b), ("sffgpu_sample_steer", "center6", _call_sample_steer),
+                     ("sffgpu_forest_create", "roots6", _call_forest_roots), ("sffgpu_forest_create", "goal", _call_forest_goal),
+                     ("sffgpu_rrt_create", "roots6", _call_rrt_roots), ("sffgpu_rrt_create", "goal", _call_rrt_goal)]
+
+
+@pytest.fixture(scope="module")
+def triang_ctx(S):
+    sc = common.scenario("triang")
+    ctx = S.Context(0)
+    ctx.upload_env(sc["env"])
+    ctx.upload_robot(sc["robot"])
+    yield ctx, sc
+    ctx.close()
+
+
+@pytest.mark.parametrize("fn,arg,call", POSE_ENTRY_POINTS, ids=["%s-%s" % (f, a) for f, a, _ in POSE_ENTRY_POINTS])
+def test_poses_outside_the_domain_are_refused(S, triang_ctx, fn, arg, call):
+    ctx, sc = triang_ctx
+    good = sc["xml_points"][:3].copy()
+    good[:, 3:] = [[0.1, -0.2, 0.3], [3.0, -3.0, 7.0], [-0.5, 0.0, 0.5]]
+    want = call(S, ctx, sc, good)
+    for bad_value, slot, word in ((np.nan, 4, "not finite"), (np.inf, 0, "not finite"), (-np.inf, 5, "not finite"),
+                                  (2e6, 3, "angle"), (-2e6, 5, "angle"), (float(np.nextafter(TRIG_DOMAIN, np.inf)), 4, "angle")):
+        rows = good.copy()
+        rows[2, slot] = bad_value
+        with pytest.raises(S.SffGpuError) as e:
+            call(S, ctx, sc, rows)
+        msg = str(e.value)
+        assert "error -1" in msg and fn in msg and arg in msg and word in msg, msg        # SFFGPU_ERR_ARG, names the argument ...
+        assert "row %d" % (0 if arg == "goal" else 2) in msg, msg                          # ... and the row
+    # the bound itself and its neighbour towards zero are angles like any other; x y z may be as large as they like
+    for v in (TRIG_DOMAIN, float(np.nextafter(TRIG_DOMAIN, 0.0)), -float(np.nextafter(TRIG_DOMAIN, 0.0))):
+        rows = good.copy()
+        rows[2, 3] = v
+        call(S, ctx, sc, rows)
+    # the context still answers a normal call, with the same answer as before
+    again = call(S, ctx, sc, good)
+    for a, b in zip(again, want) if isinstance(want, tuple) else [(again, want)]:
+        assert np.array_equal(a, b)
+    assert np.array_equal(ctx.collide_poses(good), [O.World(sc["env"], sc["robot"], O.TRIG_PORTABLE).collide(p) for p in good])
