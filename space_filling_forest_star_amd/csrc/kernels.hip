@@ -1291,26 +1291,10 @@ __device__ __forceinline__ bool dist2_far(double dd, double mag, double rr) {   
 
 // Clearance bits: true when a robot whose MODEL ORIGIN is at c provably touches nothing in any rotation (the
 // exact test would find a separating axis for every pair), so the traversal and the exact tests can be skipped.
-// Points outside the grid are farther than the build threshold from the environment's box.
-__device__ __forceinline__ bool surely_clear(const EnvView& env, const double* c) {
-  if (!env.clear_bits) return false;
-  const double fx = (c[0] - env.clear_org[0]) * env.clear_inv, fy = (c[1] - env.clear_org[1]) * env.clear_inv,
-               fz = (c[2] - env.clear_org[2]) * env.clear_inv;
-  if (!(fx == fx && fy == fy && fz == fz)) return false;
-  if (fx < 0 || fy < 0 || fz < 0 || fx >= env.clear_n[0] || fy >= env.clear_n[1] || fz >= env.clear_n[2]) return true;
-  const long long idx = ((long long)(int)fz * env.clear_n[1] + (int)fy) * env.clear_n[0] + (int)fx;
-  return (env.clear_bits[idx >> 5] >> (idx & 31)) & 1u;
-}
+// (surely_clear_in: kernels_dev.h, "clearance bits")
+__device__ __forceinline__ bool surely_clear(const EnvView& env, const double* c) { return surely_clear_in(env, env.clear_bits, c); }
 // the same for an UN-ROTATED robot (edge samples, src/problemStruct.h:157-165): the edge plane of the bits
-__device__ __forceinline__ bool surely_clear_edge(const EnvView& env, const double* c) {
-  if (!env.clear_bits_edge) return false;
-  const double fx = (c[0] - env.clear_org[0]) * env.clear_inv, fy = (c[1] - env.clear_org[1]) * env.clear_inv,
-               fz = (c[2] - env.clear_org[2]) * env.clear_inv;
-  if (!(fx == fx && fy == fy && fz == fz)) return false;
-  if (fx < 0 || fy < 0 || fz < 0 || fx >= env.clear_n[0] || fy >= env.clear_n[1] || fz >= env.clear_n[2]) return true;
-  const long long idx = ((long long)(int)fz * env.clear_n[1] + (int)fy) * env.clear_n[0] + (int)fx;
-  return (env.clear_bits_edge[idx >> 5] >> (idx & 31)) & 1u;
-}
+__device__ __forceinline__ bool surely_clear_edge(const EnvView& env, const double* c) { return surely_clear_in(env, env.clear_bits_edge, c); }
 
 // Conservative triangle / axis-aligned box test (box = centre c + [blo, bhi], blo <= 0 <= bhi per axis): false only when a
 // separating axis exists by more than the rounding noise (box axes, the triangle's normal, the nine edge x axis
@@ -2172,7 +2156,7 @@ __global__ __launch_bounds__(256) void k_cull(EnvView env, const double* __restr
       need[u] = val[u] && idx <= it[u].ns;
       wp[u] = nullptr;
       sh[u] = 0;
-      if (need[u]) {
+      if (need[u]) {   // (clear_slot_f64 of kernels_dev.h spelled out, the cell index in 32 bits: the call changes this kernel's code)
         const double fx = (C[0] - env.clear_org[0]) * env.clear_inv, fy = (C[1] - env.clear_org[1]) * env.clear_inv,
                      fz = (C[2] - env.clear_org[2]) * env.clear_inv;
         if (env.clear_bits_edge && fx == fx && fy == fy && fz == fz) {
@@ -2734,7 +2718,7 @@ __global__ __launch_bounds__(64 * QC_WAVES) __attribute__((amdgpu_waves_per_eu(Q
           if (fused_cull) {
             // the hit list is dead from here on (every lane holds its own hit in registers): the kept edges' start
             // points, sample steps and sample counts take its place, indexed by rank
-            // (in cells of the clearance grid, fp32: see the fused cull below)
+            // (in cells of the clearance grid, fp32: kernels_dev.h, "clearance bits")
             const float inv = (float)env.clear_inv * __frcp_rn((float)parts);
             float* tf = reinterpret_cast<float*>(h_pos);
             for (int k = 0; k < 3; ++k) {
@@ -2766,7 +2750,7 @@ __global__ __launch_bounds__(64 * QC_WAVES) __attribute__((amdgpu_waves_per_eu(Q
     // answered "free" by one bit; what is not goes onto the survivor list of the exact kernel.  The (task, chunk)
     // pairs are flattened so that eight dependent lookups are in flight at a time whatever the edge lengths are;
     // survivors are gathered in LDS and reserved on the list with one atomic per sample.
-    // Sample positions a + idx * step: far inside the slack of the bits.
+    // (How a sample is placed in the grid of the bits, and the slack it leans on: kernels_dev.h, "clearance bits".)
     SurvivorItem* list = static_cast<SurvivorItem*>(A.items);
     SurvivorItem* buf = s_surv[wave];
     int n_buf = 0;
@@ -2807,28 +2791,11 @@ __global__ __launch_bounds__(64 * QC_WAVES) __attribute__((amdgpu_waves_per_eu(Q
     if (lane == 0) A.pose_hit[i] = 0;
     if (live) {
       // the pose's own bit: the load is issued here and looked at after the edges' (one latency for everything)
-      const uint32_t* wp_pose = nullptr;
-      int sh_pose = 0;
-      bool need_pose = true;
-      if (env.clear_bits) {
-        const double fx = (qp[0] - env.clear_org[0]) * env.clear_inv, fy = (qp[1] - env.clear_org[1]) * env.clear_inv,
-                     fz = (qp[2] - env.clear_org[2]) * env.clear_inv;
-        if (fx == fx && fy == fy && fz == fz) {
-          if (fx < 0 || fy < 0 || fz < 0 || fx >= env.clear_n[0] || fy >= env.clear_n[1] || fz >= env.clear_n[2]) {
-            need_pose = false;
-          } else {
-            const long long ci = ((long long)(int)fz * env.clear_n[1] + (int)fy) * env.clear_n[0] + (int)fx;
-            wp_pose = env.clear_bits + (ci >> 5);
-            sh_pose = (int)(ci & 31);
-          }
-        }
-      }
-      const uint32_t word_pose = wp_pose ? *wp_pose : 0u;
+      ClearSlot pose{true, nullptr, 0};
+      if (env.clear_bits) pose = clear_slot_f64(env, env.clear_bits, qp);
+      const uint32_t word_pose = pose.wp ? *pose.wp : 0u;
       // lane r < nnb = the kept edge of rank r; the parent edge (task 0) is uniform.  Positions in cells of the
-      // clearance grid, in fp32: cell = a + idx * step is off the exact kernel's fp64 sample position by less than
-      // 1e-6 * (cells per axis) cells - the slack Ctx::build_clearance puts into the bits for exactly this
-      // (steps in fp32 with the hardware reciprocal: a relative 1e-7 on a step that spans a few cells is far inside
-      // the slack of the bits)
+      // clearance grid, in fp32 (kernels_dev.h, "clearance bits")
       const float inv0 = (float)env.clear_inv * __frcp_rn((float)parts0);
       const float g0[3] = {(float)((exp[0] - env.clear_org[0]) * env.clear_inv), (float)((exp[1] - env.clear_org[1]) * env.clear_inv),
                            (float)((exp[2] - env.clear_org[2]) * env.clear_inv)};
@@ -2847,11 +2814,8 @@ __global__ __launch_bounds__(64 * QC_WAVES) __attribute__((amdgpu_waves_per_eu(Q
       const int32_t* NS = s_id[wave];
       int32_t* tab = s_tab[wave];
       const float nxd = (float)env.clear_n[0], nyd = (float)env.clear_n[1], nzd = (float)env.clear_n[2];
-      // Eight consecutive samples of an edge lie within 0.4 units of the fifth one (the sample spacing never exceeds
-      // the 0.1 of src/problemStruct.h:121), and the bits are built with that reach on top (Ctx::build_clearance): ONE
-      // lookup answers a group of eight samples, a lane takes a group, a step of the wave eight (task, chunk) pairs.
-      // A group that is not clear goes to the exact kernel whole.  tab[]: pair -> (task << 16 | chunk), built in
-      // windows of QC_TAB pairs.
+      // ONE lookup answers a group of eight samples (clear_group), a lane takes a group, a step of the wave eight
+      // (task, chunk) pairs.  tab[]: pair -> (task << 16 | chunk), built in windows of QC_TAB pairs.
       const int pu = lane >> 3, g = lane & 7;
       for (int w0 = 0; w0 < P; w0 += QC_TAB) {
         __builtin_amdgcn_wave_barrier();
@@ -2875,14 +2839,12 @@ __global__ __launch_bounds__(64 * QC_WAVES) __attribute__((amdgpu_waves_per_eu(Q
             a0 = tt[0]; a1 = tt[1]; a2 = tt[2]; d0 = tt[4]; d1 = tt[5]; d2 = tt[6];
             ns = NS[t - 1];
           }
-          const int first = 1 + 64 * c + 8 * g;                 // the group's first sample
-          bool need = valid && first <= ns;
-          const int left = ns - first + 1;                      // valid samples from there on
-          const int probe = first + 4 <= ns ? first + 4 : ns;   // within four steps of every valid sample of the group
+          const ClearGroup gr = clear_group(c, g, ns);
+          bool need = valid && gr.any;
           const uint32_t* wp = nullptr;
           int sh = 0;
-          if (need && env.clear_bits_edge) {
-            const float td = (float)probe;
+          if (need && env.clear_bits_edge) {   // (the fp32 cell of an edge sample: kernels_dev.h, "clearance bits")
+            const float td = (float)gr.probe;
             const float fx = __builtin_fmaf(td, d0, a0), fy = __builtin_fmaf(td, d1, a1), fz = __builtin_fmaf(td, d2, a2);
             if (fx >= 0 && fy >= 0 && fz >= 0 && fx < nxd && fy < nyd && fz < nzd) {   // (the grid has fewer than 2^31 cells)
               const uint32_t ci = ((uint32_t)(int)fz * (uint32_t)env.clear_n[1] + (uint32_t)(int)fy) * (uint32_t)env.clear_n[0] + (uint32_t)(int)fx;
@@ -2894,10 +2856,7 @@ __global__ __launch_bounds__(64 * QC_WAVES) __attribute__((amdgpu_waves_per_eu(Q
           }
           const uint32_t word = wp ? *wp : 0u;
           if (wp && ((word >> sh) & 1u)) need = false;
-          unsigned long long m = need ? (((left >= 8 ? 0xffULL : ((1ULL << left) - 1ULL))) << (8 * g)) : 0ULL;
-          m |= __shfl_xor(m, 1);
-          m |= __shfl_xor(m, 2);
-          m |= __shfl_xor(m, 4);
+          const unsigned long long m = clear_group_mask(need, gr.left, g);
           const bool lead = g == 0 && m != 0ULL;
           if (__any(lead)) {
             surv_emit(buf, n_buf, lead, lane, (int32_t)(i * stride + t), c, m);
@@ -2905,7 +2864,7 @@ __global__ __launch_bounds__(64 * QC_WAVES) __attribute__((amdgpu_waves_per_eu(Q
           }
         }
       }
-      if (need_pose && !((word_pose >> sh_pose) & 1u)) {   // (uniform)
+      if (pose.need && !((word_pose >> pose.sh) & 1u)) {   // (uniform)
         if (lane == 0) buf[n_buf] = SurvivorItem{-1 - i, 0, 0ULL};
         ++n_buf;   // (flushed at 64: there is room)
       }
@@ -3070,14 +3029,13 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(QB_OCC))) v
   const float nxd = (float)env.clear_n[0], nyd = (float)env.clear_n[1], nzd = (float)env.clear_n[2];
   const bool have_env = env.n_tri != 0;
   auto group_addr = [&](bool valid, const float* tt, int ns, int c, int gi, bool& need, int& left, const uint32_t*& wp, int& sh) {
-    const int first = 1 + 64 * c + 8 * gi;
-    need = valid && first <= ns;
-    left = ns - first + 1;
-    const int probe = first + 4 <= ns ? first + 4 : ns;
+    const ClearGroup gr = clear_group(c, gi, ns);
+    need = valid && gr.any;
+    left = gr.left;
     wp = nullptr;
     sh = 0;
-    if (need && env.clear_bits_edge) {
-      const float td = (float)probe;
+    if (need && env.clear_bits_edge) {   // (the fp32 cell of an edge sample: kernels_dev.h, "clearance bits")
+      const float td = (float)gr.probe;
       const float fx = __builtin_fmaf(td, tt[4], tt[0]), fy = __builtin_fmaf(td, tt[5], tt[1]), fz = __builtin_fmaf(td, tt[6], tt[2]);
       if (fx >= 0 && fy >= 0 && fz >= 0 && fx < nxd && fy < nyd && fz < nzd) {
         const uint32_t ci = ((uint32_t)(int)fz * (uint32_t)env.clear_n[1] + (uint32_t)(int)fy) * (uint32_t)env.clear_n[0] + (uint32_t)(int)fx;
@@ -3135,7 +3093,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(QB_OCC))) v
     if (s == S - 1) s_pref[S] = inc;
     // the pose's own clearance bit
     need_pose = evaluate && have_env;
-    if (need_pose && env.clear_bits) {
+    if (need_pose && env.clear_bits) {   // (clear_slot_f64 of kernels_dev.h spelled out, with the load: the call costs this kernel 14 scalar spills)
       const double* q3 = A.newpos + 6 * (size_t)i;
       const double fx = (q3[0] - env.clear_org[0]) * env.clear_inv, fy = (q3[1] - env.clear_org[1]) * env.clear_inv,
                    fz = (q3[2] - env.clear_org[2]) * env.clear_inv;
@@ -3348,6 +3306,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(QB_OCC))) v
       A.seg_ns[slot] = ns;
       A.first_hit[slot] = 0x7fffffff;
       A.seg_ovf[slot] = 0;
+      // (the edge in cells of the clearance grid: kernels_dev.h, "clearance bits")
       const float inv = (float)env.clear_inv * __frcp_rn((float)parts);
       for (int k = 0; k < 3; ++k) {
         s_T[s][1 + rank][k] = (float)((ea[k] - env.clear_org[k]) * env.clear_inv);
@@ -3391,10 +3350,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(QB_OCC))) v
   auto settle = [&](bool need, int left, const uint32_t* wp, int sh, uint32_t word, int s, int t, int c) {
     const int gi = lane & 7;
     if (wp && ((word >> sh) & 1u)) need = false;
-    unsigned long long m = need ? (((left >= 8 ? 0xffULL : ((1ULL << left) - 1ULL))) << (8 * gi)) : 0ULL;
-    m |= __shfl_xor(m, 1);
-    m |= __shfl_xor(m, 2);
-    m |= __shfl_xor(m, 4);
+    const unsigned long long m = clear_group_mask(need, left, gi);
     const bool lead = gi == 0 && m != 0ULL;
     if (lead) s_need[s][t] = 1;
     add_surv(lead, (int32_t)(s_map[s] * stride + t), c, m);
@@ -4045,7 +4001,8 @@ __global__ __launch_bounds__(256) void k_settle(SettleArgs A) {
 // (the sq_* loads that go past the vector L1, sq_drain and lemire_pick: kernels_dev.h)
 
 // isPathFree's common case INLINE: every sample of the edge lies in a cell the clearance bits (edge plane) call clear - the
-// same placement arithmetic as sq_path_free's first phase, so the same bits are asked; edges of up to 512 samples.  True =
+// placement of kernels_dev.h ("clearance bits": the edge in cells and the fp32 cell, spelled out here, in
+// sq_edges_clear_probe and in sq_path_free), so the same bits are asked; edges of up to 512 samples.  True =
 // free, the reference's counters advanced; false = undecided, nothing touched: the caller runs sq_path_free (out of line:
 // its call saves and restores a good part of a wavefront's registers - 1.5-2 us on the wavefront everybody waits for).
 __device__ __forceinline__ bool sq_edge_clear_fast(const EnvView& env, const double* a, const double* b, int lane,
@@ -4114,6 +4071,7 @@ __device__ __forceinline__ void sq_edges_clear_probe(const EnvView& env, const d
     ns_out[e] = ns;
     if (ns > 256) continue;
     can[e] = true;
+    // (the edge in cells and the fp32 cell: kernels_dev.h, "clearance bits")
     const float inv = (float)env.clear_inv * __frcp_rn((float)parts);
     const float g0 = (float)((a[e][0] - env.clear_org[0]) * env.clear_inv), g1 = (float)((a[e][1] - env.clear_org[1]) * env.clear_inv),
                 g2 = (float)((a[e][2] - env.clear_org[2]) * env.clear_inv);
@@ -4164,11 +4122,10 @@ __device__ __attribute__((noinline)) bool sq_path_free(const EnvView& env, const
   int fh = 0x7fffffff;
   if (env.n_tri != 0) {
     DBG_DECL
-    // The samples' clearance bits first, placed like k_query_classify's fused cull places them: in cells of the clearance
-    // grid, fp32, a + idx * step (the bits carry the slack for exactly that) - one wavefront is bound by its own
-    // instruction stream, and the exact positions cost three fp64 divisions per sample (measured on one box: 14.4 vs
-    // 19.4 us per iteration).  Four chunks' lookups are in flight together; only a chunk with a sample left goes through
-    // the exact test.
+    // The samples' clearance bits first, placed in fp32 in cells of the clearance grid (kernels_dev.h, "clearance
+    // bits") - one wavefront is bound by its own instruction stream, and the exact positions cost three fp64 divisions
+    // per sample (measured on one box: 14.4 vs 19.4 us per iteration).  Four chunks' lookups are in flight together; only
+    // a chunk with a sample left goes through the exact test.
     const float inv = (float)env.clear_inv * __frcp_rn((float)parts);
     const float g0 = (float)((a[0] - env.clear_org[0]) * env.clear_inv), g1 = (float)((a[1] - env.clear_org[1]) * env.clear_inv),
                 g2 = (float)((a[2] - env.clear_org[2]) * env.clear_inv);

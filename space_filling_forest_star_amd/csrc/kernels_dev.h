@@ -74,6 +74,79 @@ __device__ __forceinline__ int lemire_pick(unsigned long long word, unsigned lon
   return (int)hi;
 }
 
+// ---- clearance bits: the placement arithmetic and the slack it leans on.  The bits (EnvView::clear_bits: a posed robot,
+// clear_bits_edge: an un-rotated edge sample) answer ~97 % of the collision work with one lookup, and every path that asks
+// them must ask the same bit for the same sample.  The contract with Ctx::build_clearance (engine.cpp) is stated HERE and
+// nowhere else:
+//  - A pose's cell is taken in fp64 from the model origin: (c - clear_org) * clear_inv per axis.
+//  - An edge's samples are placed in fp32, in cells of the grid, at g + idx * d: g = (float)((a - clear_org) * clear_inv)
+//    is the start point, d = (float)(b - a) * ((float)clear_inv * __frcp_rn((float)parts)) one sample step - the step
+//    with the HARDWARE reciprocal of the edge's part count (a relative 1e-7 on a step that spans a few cells).  The exact
+//    kernels place the same sample in fp64 (edge_sample_pos); the fp32 cell is off that position by less than
+//    1e-6 * (cells per axis) cells, and build_clearance puts exactly that into the threshold of the bits.
+//  - Eight consecutive samples of an edge lie within 0.4 units of the fifth one (the sample spacing never exceeds the
+//    0.1 of src/problemStruct.h:121), and the EDGE plane is built with that reach on top: one probe answers a group of
+//    eight samples (clear_group); a group that is not clear goes to the exact kernel whole (clear_group_mask).
+//  - The grid spans the environment's box inflated by the build threshold: a cell outside it is clear without a word.
+//    A NaN position, or a plane that was not built, leaves the sample needed with no word to look at.
+// A slot function only computes where the bit is: the caller loads the words of all its slots together (one memory
+// latency for everything) and looks at them afterwards.
+// Change any of this together with build_clearance: a placement that drifts accepts an edge the exact test rejects.
+// The fp32 placement (the edge in cells, a sample's fp32 cell) is still spelled out at each of its sites - they point
+// here, and profiles/README.md ("Clearance lookups") says why; keep them identical to this block.
+
+// where a sample's bit is: wp = the word (null = no word to look at), sh = the bit in it; need = the bits may still say no
+struct ClearSlot {
+  bool need;
+  const uint32_t* wp;
+  int sh;
+};
+// a position c (a pose's model origin, an exact edge sample), fp64, in a plane `bits` that was built (not null).  The pose
+// and the edge plane differ in the pointer alone.
+__device__ __forceinline__ ClearSlot clear_slot_f64(const EnvView& env, const uint32_t* bits, const double* c) {
+  ClearSlot s{true, nullptr, 0};
+  const double fx = (c[0] - env.clear_org[0]) * env.clear_inv, fy = (c[1] - env.clear_org[1]) * env.clear_inv,
+               fz = (c[2] - env.clear_org[2]) * env.clear_inv;
+  if (fx == fx && fy == fy && fz == fz) {
+    if (fx < 0 || fy < 0 || fz < 0 || fx >= env.clear_n[0] || fy >= env.clear_n[1] || fz >= env.clear_n[2]) {
+      s.need = false;                                       // beyond the inflated box of the environment
+    } else {
+      const long long ci = ((long long)(int)fz * env.clear_n[1] + (int)fy) * env.clear_n[0] + (int)fx;
+      s.wp = bits + (ci >> 5);
+      s.sh = (int)(ci & 31);
+    }
+  }
+  return s;
+}
+// the whole question for one position, load included: true = the plane `bits` calls it clear
+__device__ __forceinline__ bool surely_clear_in(const EnvView& env, const uint32_t* bits, const double* c) {
+  if (!bits) return false;
+  const double fx = (c[0] - env.clear_org[0]) * env.clear_inv, fy = (c[1] - env.clear_org[1]) * env.clear_inv,
+               fz = (c[2] - env.clear_org[2]) * env.clear_inv;
+  if (!(fx == fx && fy == fy && fz == fz)) return false;
+  if (fx < 0 || fy < 0 || fz < 0 || fx >= env.clear_n[0] || fy >= env.clear_n[1] || fz >= env.clear_n[2]) return true;
+  const long long idx = ((long long)(int)fz * env.clear_n[1] + (int)fy) * env.clear_n[0] + (int)fx;
+  return (bits[idx >> 5] >> (idx & 31)) & 1u;
+}
+// group g (0..7) of chunk `chunk` of an edge of ns samples: any = it has a sample, left = valid samples from its first one
+// on, probe = the sample to look up (within four steps of every valid sample of the group)
+struct ClearGroup {
+  bool any;
+  int left, probe;
+};
+__device__ __forceinline__ ClearGroup clear_group(int chunk, int g, int ns) {
+  const int first = 1 + 64 * chunk + 8 * g;
+  return ClearGroup{first <= ns, ns - first + 1, first + 4 <= ns ? first + 4 : ns};
+}
+// the chunk's mask of samples for the exact kernel, in all eight lanes of the chunk: every valid sample of the groups still needed
+__device__ __forceinline__ unsigned long long clear_group_mask(bool need, int left, int g) {
+  unsigned long long m = need ? (((left >= 8 ? 0xffULL : ((1ULL << left) - 1ULL))) << (8 * g)) : 0ULL;
+  m |= __shfl_xor(m, 1);
+  m |= __shfl_xor(m, 2);
+  m |= __shfl_xor(m, 4);
+  return m;
+}
+
 // ---- survivors of the clearance cull -> items of the exact kernel.  The lead lanes (lane % 8 == 0) of a step each hold one
 // (edge slot, 64-sample chunk, mask) survivor.  The exact kernel's length is its longest item (one wavefront per item:
 // broad phase of the masked samples' swept box, then every sample against every candidate triangle), so a survivor with
@@ -413,6 +486,7 @@ __device__ __forceinline__ void sample_finish(int tid, bool valid, int i, int pa
         // the parent edge, isPathFree(expanded, newPoint) (src/forest.h:246): its length is parentDistance
         const double parts0 = pd / 0.1;   // = edge_parts(c, o)
         r.ns0 = edge_samples(parts0);
+        // (the edge in cells of the clearance grid: "clearance bits" above)
         const float inv0 = (float)tmp.clear_inv * __frcp_rn((float)parts0);
         for (int k = 0; k < 3; ++k) {
           r.t0[k] = (float)((c[k] - tmp.clear_org[k]) * tmp.clear_inv);

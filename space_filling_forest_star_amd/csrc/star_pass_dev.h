@@ -188,6 +188,7 @@ template <bool COH> __device__ __forceinline__ void star_pass_sample(const Resol
         const double parts = edge_parts(qp, mp);
         ns_f = edge_samples(parts);
         nch_f = ns_f > 0 ? (ns_f + 63) >> 6 : 0;
+        // (the edge in cells of the clearance grid, here and below: kernels_dev.h, "clearance bits")
         const float inv = (float)env.clear_inv * __frcp_rn((float)parts);
         for (int q = 0; q < 3; ++q) {
           ef[q] = (float)((qp[q] - env.clear_org[q]) * env.clear_inv);
@@ -246,22 +247,19 @@ template <bool COH> __device__ __forceinline__ void star_pass_sample(const Resol
       __builtin_amdgcn_wave_barrier();
       const int wn = P - w0 < STAR_TAB ? P - w0 : STAR_TAB;
       for (int q0 = 0; q0 < wn; q0 += 8) {
-        // eight consecutive samples of an edge lie within 0.4 units of the fifth one (the sample spacing never exceeds
-        // the 0.1 of src/problemStruct.h:121) and the bits are built with that reach on top (Ctx::build_clearance): one
-        // lookup answers a group of eight samples, a lane takes a group, a step of the wave eight (edge, chunk) pairs
+        // one lookup answers a group of eight samples (kernels_dev.h, "clearance bits"), a lane takes a group, a step of
+        // the wave eight (edge, chunk) pairs
         const bool valid = q0 + pu < wn;
         const int ent = valid ? tab[q0 + pu] : 0;
         const int e = ent >> 16, ch = ent & 0xffff;
         const float* ee = L.edge[wave][e];
         const int ns = __float_as_int(ee[3]);
-        const int first = 1 + 64 * ch + 8 * gq;
-        bool need = valid && first <= ns;
-        const int left = ns - first + 1;
-        const int probe = first + 4 <= ns ? first + 4 : ns;
+        const ClearGroup gr = clear_group(ch, gq, ns);
+        bool need = valid && gr.any;
         const uint32_t* wp = nullptr;
         int sh = 0;
-        if (need && env.clear_bits_edge) {
-          const float td = (float)probe;
+        if (need && env.clear_bits_edge) {   // (the fp32 cell of an edge sample: kernels_dev.h, "clearance bits")
+          const float td = (float)gr.probe;
           const float fx = __builtin_fmaf(td, ee[4], ee[0]), fy = __builtin_fmaf(td, ee[5], ee[1]), fz = __builtin_fmaf(td, ee[6], ee[2]);
           if (fx >= 0 && fy >= 0 && fz >= 0 && fx < nxd && fy < nyd && fz < nzd) {
             const uint32_t ci = ((uint32_t)(int)fz * (uint32_t)env.clear_n[1] + (uint32_t)(int)fy) * (uint32_t)env.clear_n[0] + (uint32_t)(int)fx;
@@ -273,10 +271,7 @@ template <bool COH> __device__ __forceinline__ void star_pass_sample(const Resol
         }
         const uint32_t word = wp ? *wp : 0u;
         if (wp && ((word >> sh) & 1u)) need = false;
-        unsigned long long m = need ? (((left >= 8 ? 0xffULL : ((1ULL << left) - 1ULL))) << (8 * gq)) : 0ULL;
-        m |= __shfl_xor(m, 1);
-        m |= __shfl_xor(m, 2);
-        m |= __shfl_xor(m, 4);
+        const unsigned long long m = clear_group_mask(need, gr.left, gq);
         const bool lead = gq == 0 && m != 0ULL && env.n_tri != 0;
         if (__any(lead)) {
           if (lead) L.any[wave][e] = 1;
