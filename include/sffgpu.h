@@ -42,7 +42,8 @@ int sffgpu_mesh_upload(sffgpu_ctx* ctx, int role, const double* tri9, int n_tri)
  * must be finite and every angle must lie within +-2^20 * pi/2 (about 1.647e6; SFFP_TRIG_DOMAIN of csrc/sff_pmath.h),
  * the range over which the library's sine and cosine are accurate to 1 ulp.  Angles need not be normalised to [-pi, pi).
  * A row outside this is refused with SFFGPU_ERR_ARG before anything is launched; sffgpu_last_error names the argument
- * and the row. */
+ * and the row.  Positions (meshes, limits, poses) carry no bound of their own: results are tested to be the fp64 reference's,
+ * bit for bit, for worlds up to |coordinate| = 2^22 (tests/test_gpu_far_from_origin.py), about a UTM northing. */
 
 /* Environment::Collide(position) (src/environment.h:306-316 -> RAPID_Collide :268-276):
  * hit[i] = 1 if the robot posed at pos6[i] = (x y z yaw pitch roll) touches any ENV triangle. */

@@ -45,7 +45,9 @@ XML_POINTS = {
 }
 
 
-def scenario(name):
+def scenario(name, shift=None):
+    """shift = (dx, dy, dz): the same world moved away from the origin - every vertex of the environment mesh, the three
+    position limit pairs and the positions of the XML points; the robot mesh, the distances and the angles stay"""
     env, rob, scale, lim, dt, sd, dim = SCENARIOS[name]
     m = meshes()
     sc = dict(env=scaled(m[env], scale), robot=scaled(m[rob], scale), limits=lim, dist_tree=dt, sampling_dist=sd,
@@ -54,6 +56,15 @@ def scenario(name):
         pts = np.zeros((len(XML_POINTS[name]), 6))
         pts[:, :3] = np.array(XML_POINTS[name], dtype=np.float64) * scale
         sc["xml_points"] = pts
+    if shift is not None:
+        s = np.array(shift, dtype=np.float64)
+        assert s.shape == (3,)
+        assert dim == 6 or s[2] == 0.0, "a 2-D world lies in z = 0"
+        sc["env"] = np.ascontiguousarray(sc["env"] + np.tile(s, 3))
+        sc["limits"] = [float(lim[2 * a + e] + s[a]) for a in range(3) for e in range(2)]
+        if sc["xml_points"] is not None:
+            sc["xml_points"][:, :3] += s
+        sc["shift"] = s
     return sc
 
 

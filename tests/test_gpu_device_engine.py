@@ -45,8 +45,8 @@ class engine:
                 os.environ[k] = v
 
 
-def make(S, ctx, name, wave, iters, seed, n_roots=5, budget=0, which="device", optimize=False, goal_offset=None, **env):
-    sc, w = load_world(ctx, name)
+def make(S, ctx, name, wave, iters, seed, n_roots=5, budget=0, which="device", optimize=False, goal_offset=None, shift=None, **env):
+    sc, w = load_world(ctx, name, shift)
     roots = sc["xml_points"][:n_roots] if sc["xml_points"] is not None else \
         common.free_roots(w.collide, sc["limits"], n_roots, seed=seed, dim=sc["dim"])
     kw = dict(dist_tree=sc["dist_tree"], sampling_dist=sc["sampling_dist"], dim=sc["dim"], max_iterations=iters,

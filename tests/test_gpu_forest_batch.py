@@ -29,12 +29,12 @@ def pool(S):
         c.close()
 
 
-_oracle_runs = {}   # (scenario, seed, iterations, optimize) -> the oracle forest after its run (cases share members)
+_oracle_runs = {}   # (scenario, seed, iterations, optimize, shift) -> the oracle forest after its run (cases share members)
 
 
-def member(S, ctx, name, seed, iters, optimize=False, wave=1, n_roots=5, goal_offset=None, priority_bias=0.0, **env):
+def member(S, ctx, name, seed, iters, optimize=False, wave=1, n_roots=5, goal_offset=None, priority_bias=0.0, shift=None, **env):
     """one member on ITS context, the way test_gpu_device_engine.make builds a forest: roots of its own seed"""
-    sc, w = load_world(ctx, name)
+    sc, w = load_world(ctx, name, shift)
     roots = sc["xml_points"][:n_roots] if sc["xml_points"] is not None else \
         common.free_roots(w.collide, sc["limits"], n_roots, seed=seed, dim=sc["dim"])
     kw = dict(dist_tree=sc["dist_tree"], sampling_dist=sc["sampling_dist"], dim=sc["dim"], max_iterations=iters,
@@ -43,7 +43,7 @@ def member(S, ctx, name, seed, iters, optimize=False, wave=1, n_roots=5, goal_of
         g = roots[0].copy()
         g[:3] += np.array(goal_offset, dtype=np.float64)
         kw["goal"] = g
-    key = (name, seed, iters, optimize)
+    key = (name, seed, iters, optimize, None if shift is None else tuple(shift))
     plain = wave == 1 and goal_offset is None and priority_bias == 0.0 and n_roots == 5
     if plain and key in _oracle_runs:
         fo = _oracle_runs[key]

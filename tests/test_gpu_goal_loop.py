@@ -32,12 +32,12 @@ def pool(S):
 _oracle = {}   # job -> the oracle forest after its run: computed once, shared by the tests that use the job, never advanced again
 
 
-def pair(S, ctx, name, seed, iters, n_roots, offset=None, optimize=False, knob=True, **env):
+def pair(S, ctx, name, seed, iters, n_roots, offset=None, optimize=False, knob=True, shift=None, **env):
     """(oracle after its whole run, the library's forest before its first wave) of one goal job"""
     if knob:
         env = dict(env, **KNOB)
-    fo, fg = member(S, ctx, name, seed, iters, optimize=optimize, n_roots=n_roots, goal_offset=offset, **env)
-    key = (name, seed, iters, n_roots, tuple(offset), optimize)
+    fo, fg = member(S, ctx, name, seed, iters, optimize=optimize, n_roots=n_roots, goal_offset=offset, shift=shift, **env)
+    key = (name, seed, iters, n_roots, tuple(offset), optimize) + (() if shift is None else (tuple(shift),))
     if key not in _oracle:
         fo.run()
         _oracle[key] = fo

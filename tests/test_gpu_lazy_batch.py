@@ -60,15 +60,15 @@ def job(name, a, b, seed, iters, optimize, skip=0):
     return (name, a, b, seed, iters, bool(optimize), skip)
 
 
-def lazy_member(S, ctx, jb, on=1, wave=0):
+def lazy_member(S, ctx, jb, on=1, wave=0, shift=None):
     """(the job's oracle - run or not yet, run_oracles -, the library's session before its first iteration) of one lazy edge
     on ITS context: root = point a, goal = point b of the map's own points, else of the free roots test_lazy_edge_rrt_identical uses"""
     name, a, b, seed, iters, optimize, skip = jb
-    sc, w = load_world(ctx, name)
+    sc, w = load_world(ctx, name, shift)
     pts = sc["xml_points"] if sc["xml_points"] is not None else common.free_roots(w.collide, sc["limits"], 6, seed=3, dim=sc["dim"])
     kw = dict(goal=pts[b], dist_tree=sc["dist_tree"], sampling_dist=sc["sampling_dist"], dim=sc["dim"], optimize=optimize,
               max_iterations=iters, seed=seed, lazy_edge=True, rng_skip=skip)
-    ro = _oracle.get(jb) or O.Rrt(w, pts[a:a + 1], sc["limits"], **kw)
+    ro = (_oracle.get(jb) if shift is None else None) or O.Rrt(w, pts[a:a + 1], sc["limits"], **kw)
     with knob(on):
         rg = S.Rrt(ctx, pts[a:a + 1], sc["limits"], wave=wave, **kw)
     rg.n_trees = 1

@@ -24,8 +24,8 @@ def ctx(S):
     c.close()
 
 
-def load_world(ctx, name):
-    sc = common.scenario(name)
+def load_world(ctx, name, shift=None):
+    sc = common.scenario(name, shift)
     ctx.upload_env(sc["env"])
     ctx.upload_robot(sc["robot"])
     w = O.World(sc["env"], sc["robot"], O.TRIG_PORTABLE)

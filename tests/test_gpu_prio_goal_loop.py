@@ -32,12 +32,12 @@ def pool(S):
 _oracle = {}   # job -> the oracle forest after its run: computed once, shared by the tests that use the job, never advanced again
 
 
-def pair(S, ctx, name, seed, iters, n_roots, offset, bias=0.95, optimize=False, knob=True, **env):
+def pair(S, ctx, name, seed, iters, n_roots, offset, bias=0.95, optimize=False, knob=True, shift=None, **env):
     """(oracle after its whole run, the library's forest before its first wave) of one priority + goal job"""
     if knob:
         env = dict(env, **KNOB)
-    fo, fg = member(S, ctx, name, seed, iters, optimize=optimize, n_roots=n_roots, goal_offset=offset, priority_bias=bias, **env)
-    key = (name, seed, iters, n_roots, tuple(offset), bias, optimize)
+    fo, fg = member(S, ctx, name, seed, iters, optimize=optimize, n_roots=n_roots, goal_offset=offset, priority_bias=bias, shift=shift, **env)
+    key = (name, seed, iters, n_roots, tuple(offset), bias, optimize) + (() if shift is None else (tuple(shift),))
     if key not in _oracle:
         fo.run()
         _oracle[key] = fo

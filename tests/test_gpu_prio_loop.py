@@ -31,12 +31,12 @@ def pool(S):
 _oracle = {}   # job -> the oracle forest after its run: computed once, shared by the tests that use the job, never advanced again
 
 
-def pair(S, ctx, name, seed, iters, bias, n_roots=5, optimize=False, knob=True, **env):
+def pair(S, ctx, name, seed, iters, bias, n_roots=5, optimize=False, knob=True, shift=None, **env):
     """(oracle after its whole run, the library's forest before its first wave) of one job"""
     if knob:
         env = dict(env, **KNOB)
-    fo, fg = member(S, ctx, name, seed, iters, optimize=optimize, n_roots=n_roots, priority_bias=bias, **env)
-    key = (name, seed, iters, bias, n_roots, optimize)
+    fo, fg = member(S, ctx, name, seed, iters, optimize=optimize, n_roots=n_roots, priority_bias=bias, shift=shift, **env)
+    key = (name, seed, iters, bias, n_roots, optimize) + (() if shift is None else (tuple(shift),))
     if key not in _oracle:
         if bias != 0.0:   # (member() has run - and keeps - the plain ones)
             fo.run()

@@ -31,10 +31,11 @@ def pool(S):
         c.close()
 
 
-def member(S, ctx, name, seed, iters, optimize=False, n_roots=1, goal=False, bias=0.0, wave=0, lazy_edge=False, run_oracle=True):
+def member(S, ctx, name, seed, iters, optimize=False, n_roots=1, goal=False, bias=0.0, wave=0, lazy_edge=False, run_oracle=True,
+           shift=None):
     """one member on ITS context, built the way test_rrt_identical builds a session: the map's own points where it has
     some, free roots of the member's seed otherwise; the oracle of the same job is created, not yet run (run_oracles)"""
-    sc, w = load_world(ctx, name)
+    sc, w = load_world(ctx, name, shift)
     pts = sc["xml_points"] if sc["xml_points"] is not None else common.free_roots(w.collide, sc["limits"], max(6, n_roots), seed=seed,
                                                                                  dim=sc["dim"])
     roots = pts[:n_roots]
