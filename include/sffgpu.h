@@ -215,6 +215,25 @@ int sffgpu_forest_path_plan(sffgpu_forest* f, int i, int j, int32_t* node_ids, i
 /* SpaceForest::smoothPaths (src/forest.h:464-511) on the paths extracted by sffgpu_forest_paths: shortcuts
  * every path with batched isPathFree checks; dist receives the updated cost matrix, path_plan the new plans. */
 int sffgpu_forest_smooth_paths(sffgpu_forest* f, double* dist);
+/* Path smoothing on the device: the same walk for every path of n forests (each after its sffgpu_forest_paths) in one launch
+ * of k_smooth_paths, one wavefront per path, each candidate edge tested only when the walk reaches it - plans, costs (bit for
+ * bit) and the reference-equivalent counters come out as n calls of sffgpu_forest_smooth_paths leave them.  dist: n pointers,
+ * each NULL or room for that forest's cost matrix.  A member without extracted paths returns SFFGPU_ERR_STATE with *failed =
+ * its index before anything runs; n <= 0, NULL, the same forest twice or members on different devices SFFGPU_ERR_ARG.  A
+ * member without a path, and a path of one or two entries, are fine.  If a member fails, *failed = its index (-1 otherwise),
+ * the message is on ITS context and no member has been touched.  A forest created under SFFGPU_SMOOTH_LOOP=1 takes this path
+ * (n = 1) in sffgpu_forest_smooth_paths too; SFFGPU_SMOOTH_EDGES = most edges a launch tests per path. */
+typedef struct {
+  uint64_t launches;    /* launches of k_smooth_paths the planner took part in (0 = the device loop never ran for it) */
+  uint64_t paths;       /* paths handed to the device loop (all calls) */
+  uint64_t steps;       /* steps of the walk (far ends g) decided */
+  uint64_t edges;       /* candidate edges tested = the growth of path_free_calls over those calls */
+  uint64_t host_edges;  /* ... of them, edges of steps the kernel handed to the host */
+  double ms;            /* wall time of the calls */
+} sffgpu_smooth_stats;
+int sffgpu_forest_smooth_paths_batch(sffgpu_forest* const* f, int n, double* const* dist /* n pointers, each may be NULL */,
+                                     int32_t* failed /* may be NULL */);
+int sffgpu_forest_get_smooth_stats(sffgpu_forest* f, sffgpu_smooth_stats* out);
 
 /* ---------------------------------------------------------------- RRT / RRT* / Multi-T-RRT
  * RapidExpTree<T,R> (src/rrt.h:25-44): constructor :47-83, Solve() :86-99, expandNode :128-322
@@ -282,6 +301,11 @@ int sffgpu_rrt_path_plan(sffgpu_rrt* r, int i, int j, int32_t* node_ids, int cap
  * read with sffgpu_rrt_link_plan(k).  Returns the number of link plans. */
 int sffgpu_rrt_smooth_paths(sffgpu_rrt* r);
 int sffgpu_rrt_link_plan(sffgpu_rrt* r, int k, int32_t* node_ids, int cap);
+/* The link plans of n sessions (each after its sffgpu_rrt_paths) through the device loop of
+ * sffgpu_forest_smooth_paths_batch, with its rules and its error behaviour; the plans are read with sffgpu_rrt_link_plan,
+ * the matrix stays what it was.  A session created under SFFGPU_SMOOTH_LOOP=1 takes this path in sffgpu_rrt_smooth_paths. */
+int sffgpu_rrt_smooth_paths_batch(sffgpu_rrt* const* r, int n, int32_t* failed /* may be NULL */);
+int sffgpu_rrt_get_smooth_stats(sffgpu_rrt* r, sffgpu_smooth_stats* out);
 /* lazy_edge: the solved edge's plan without its goal entry (src/lazy.h:265-272): root ... the node that reached the
  * goal; returns its length (0 = unsolved; may exceed cap) */
 int sffgpu_rrt_lazy_plan(sffgpu_rrt* r, int32_t* node_ids, int cap);

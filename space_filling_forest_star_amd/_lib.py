@@ -24,6 +24,8 @@ EXPORTED_SYMBOLS = [
     "sffgpu_forest_rounds_per_wave", "sffgpu_forest_dev_wave_begin", "sffgpu_forest_dev_round_eval",
     "sffgpu_forest_dev_round_commit", "sffgpu_forest_dev_wave_end", "sffgpu_forest_in_wave", "sffgpu_forest_round_begin", "sffgpu_forest_round_records", "sffgpu_forest_round_commit",
     "sffgpu_forest_run_batch", "sffgpu_rrt_run_batch",
+    "sffgpu_forest_smooth_paths_batch", "sffgpu_rrt_smooth_paths_batch", "sffgpu_forest_get_smooth_stats",
+    "sffgpu_rrt_get_smooth_stats",
 ]
 
 # sffgpu_allgather_fn: int fn(void* user, const void* send_dev, void* recv_dev, size_t words_i32, void* hip_stream)
@@ -79,6 +81,15 @@ class RrtStats(C.Structure):
                 ("path_free_calls", C.c_uint64), ("nn_queries", C.c_uint64), ("total_ms", C.c_double),
                 ("waves", C.c_uint64), ("speculated", C.c_uint64), ("committed", C.c_uint64), ("rng_draws", C.c_uint64),
                 ("lazy_distance", C.c_double), ("batch_launches", C.c_uint64), ("batch_host_iterations", C.c_uint64)]
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_}
+
+
+class SmoothStats(C.Structure):
+    """sffgpu_smooth_stats: what the device loop of path smoothing (k_smooth_paths) has done for one planner"""
+    _fields_ = [("launches", C.c_uint64), ("paths", C.c_uint64), ("steps", C.c_uint64), ("edges", C.c_uint64),
+                ("host_edges", C.c_uint64), ("ms", C.c_double)]
 
     def as_dict(self):
         return {k: getattr(self, k) for k, _ in self._fields_}
@@ -153,6 +164,11 @@ def lib():
     if hasattr(L, "sffgpu_rrt_run_batch"):   # (SFFGPU_LIB may name a build from before session batches; run_rrt_batch says so)
         L.sffgpu_rrt_run_batch.argtypes = [C.POINTER(C.c_void_p), C.c_int, C.c_int, c_ip]
     L.sffgpu_rrt_get_stats.argtypes = [C.c_void_p, C.POINTER(RrtStats)]
+    if hasattr(L, "sffgpu_forest_smooth_paths_batch"):   # (SFFGPU_LIB may name a build from before the device loop of path smoothing)
+        L.sffgpu_forest_smooth_paths_batch.argtypes = [C.POINTER(C.c_void_p), C.c_int, C.POINTER(c_dp), c_ip]
+        L.sffgpu_rrt_smooth_paths_batch.argtypes = [C.POINTER(C.c_void_p), C.c_int, c_ip]
+        L.sffgpu_forest_get_smooth_stats.argtypes = [C.c_void_p, C.POINTER(SmoothStats)]
+        L.sffgpu_rrt_get_smooth_stats.argtypes = [C.c_void_p, C.POINTER(SmoothStats)]
     L.sffgpu_rrt_get_nodes.argtypes = [C.c_void_p, c_dp, c_ip, c_ip, c_ip, c_ip, c_dp, c_dp]
     L.sffgpu_rrt_get_links.argtypes = [C.c_void_p, c_ip, c_ip, c_ip, c_dp, C.c_int]
     L.sffgpu_rrt_paths.argtypes = [C.c_void_p, c_dp, c_ip, C.c_int]
@@ -457,6 +473,13 @@ class Forest:
         self.ctx._chk(self.ctx._L.sffgpu_forest_smooth_paths(self.h, _dp(d)))
         return d
 
+    def smooth_stats(self):
+        """what the device loop of path smoothing has done for this forest (smooth_batch, or smooth() of a forest created
+        under SFFGPU_SMOOTH_LOOP=1); launches == 0: it never ran"""
+        s = SmoothStats()
+        self.ctx._chk(self.ctx._L.sffgpu_forest_get_smooth_stats(self.h, C.byref(s)))
+        return s.as_dict()
+
     def plan(self, i, j, cap=1 << 16):
         ids = np.zeros(cap, np.int32)
         k = self.ctx._chk(self.ctx._L.sffgpu_forest_path_plan(self.h, i, j, _ip(ids), cap))
@@ -591,12 +614,21 @@ class Rrt:
     def smooth(self, cap=1 << 16):
         """RapidExpTree::smoothPaths on the central tree's link plans (after paths()); returns the plans"""
         n = self.ctx._chk(self.ctx._L.sffgpu_rrt_smooth_paths(self.h))
+        return self.link_plans(n, cap)
+
+    def link_plans(self, n, cap=1 << 16):
         out = []
         for k in range(n):
             ids = np.zeros(cap, np.int32)
             m = self.ctx._chk(self.ctx._L.sffgpu_rrt_link_plan(self.h, k, _ip(ids), cap))
             out.append(ids[:min(m, cap)].copy())
         return out
+
+    def smooth_stats(self):
+        """what the device loop of path smoothing has done for this session; launches == 0: it never ran"""
+        s = SmoothStats()
+        self.ctx._chk(self.ctx._L.sffgpu_rrt_get_smooth_stats(self.h, C.byref(s)))
+        return s.as_dict()
 
     def links(self, cap=1 << 16):
         t, n1, n2 = (np.zeros(cap, np.int32) for _ in range(3))
@@ -847,6 +879,58 @@ def run_rrt_batch(sessions, max_iterations=0):
                    " SFFGPU_LAZY_BATCH=1, none of them twice, each on a context of its own, all on one device)" \
                    % ((", member %d" % min(bad)) if bad else "")
         raise SffGpuError(msg)
+
+
+def _smooth_error(L, rc, failed, members, what):
+    msg = "sffgpu error %d" % rc
+    if 0 <= failed < len(members):
+        msg += " (member %d): %s" % (failed, L.sffgpu_last_error(members[failed].ctx.h).decode())
+    elif rc == -1:
+        msg += ": not a smoothing batch (needs n >= 1 %s, none of them twice, all on one device)" % what
+    return SffGpuError(msg)
+
+
+def smooth_batch(forests):
+    """smoothPaths for every path of independent forests together (sffgpu_forest_smooth_paths_batch): one wavefront per path,
+    one kernel launch for all of them, launched again until every path is done; each forest ends exactly as its own smooth()
+    would leave it.  Every forest has had its paths() called; all on one device.  Returns the list of cost matrices.  An
+    error names the member it came from, and no member has been touched."""
+    forests = list(forests)
+    L = lib()
+    if not hasattr(L, "sffgpu_forest_smooth_paths_batch"):
+        raise SffGpuError("this build of libsffgpu.so has no sffgpu_forest_smooth_paths_batch")
+    arr = (C.c_void_p * max(1, len(forests)))(*[getattr(f, "h", None) for f in forests])
+    mats = []
+    for f in forests:
+        n = f.stats()["n_trees"] if getattr(f, "h", None) else 0
+        mats.append(np.zeros((n, n)))
+    dist = (c_dp * max(1, len(forests)))(*[_dp(d) for d in mats])
+    failed = C.c_int32(-1)
+    rc = L.sffgpu_forest_smooth_paths_batch(arr if forests else None, len(forests), dist, C.byref(failed))
+    if rc < 0:
+        raise _smooth_error(L, rc, failed.value, forests, "forests")
+    return mats
+
+
+def smooth_rrt_batch(sessions, cap=1 << 16):
+    """RapidExpTree::smoothPaths for the link plans of independent sessions together (sffgpu_rrt_smooth_paths_batch), each
+    after its paths(); returns, per session, the list of its smoothed link plans - what its own smooth() would return."""
+    sessions = list(sessions)
+    L = lib()
+    if not hasattr(L, "sffgpu_rrt_smooth_paths_batch"):
+        raise SffGpuError("this build of libsffgpu.so has no sffgpu_rrt_smooth_paths_batch")
+    arr = (C.c_void_p * max(1, len(sessions)))(*[getattr(r, "h", None) for r in sessions])
+    failed = C.c_int32(-1)
+    rc = L.sffgpu_rrt_smooth_paths_batch(arr if sessions else None, len(sessions), C.byref(failed))
+    if rc < 0:
+        raise _smooth_error(L, rc, failed.value, sessions, "RRT sessions")
+    out = []
+    for r in sessions:
+        n = 0
+        while r.ctx._L.sffgpu_rrt_link_plan(r.h, n, None, 0) > 0:   # (a link plan has two entries at least)
+            n += 1
+        out.append(r.link_plans(n, cap))
+    return out
 
 
 def run_distributed(forest, max_waves=0, group=None):

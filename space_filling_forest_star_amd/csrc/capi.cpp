@@ -92,6 +92,60 @@ static int run_batch_entry(Handle* const* h, int n, int32_t* failed, Eligible el
   return SFFGPU_OK;
 }
 
+// sffgpu_forest_smooth_paths_batch / sffgpu_rrt_smooth_paths_batch: the members are checked (one device, distinct handles,
+// then ready(handle): paths extracted - the first that is not ends the call with SFFGPU_ERR_STATE), run_smooth_batch walks
+// their paths, and what it throws is the failed member's error (run_batch_entry's rules)
+template <class Handle, class Ready>
+static int smooth_batch_entry(Handle* const* h, int n, int32_t* failed, Ready ready) {
+  if (failed) *failed = -1;
+  if (!h || n <= 0) return SFFGPU_ERR_ARG;
+  for (int i = 0; i < n; ++i) {
+    if (!h[i] || engine_of(h[i])->ctx->device != engine_of(h[0])->ctx->device) return SFFGPU_ERR_ARG;
+    for (int j = 0; j < i; ++j)
+      if (h[j] == h[i]) return SFFGPU_ERR_ARG;
+  }
+  for (int i = 0; i < n; ++i) {
+    const int rc = ready(h[i]);
+    if (rc != SFFGPU_OK) {
+      if (failed) *failed = i;
+      return rc;
+    }
+  }
+  std::vector<SmoothMember> members;
+  for (int i = 0; i < n; ++i) members.push_back(smooth_member(*engine_of(h[i])));
+  int bad = -1;
+  auto blame = [&](const std::string& msg) {
+    if (bad < 0) bad = 0;
+    h[bad]->owner->c->err = msg;
+    if (failed) *failed = bad;
+  };
+  try {
+    run_smooth_batch(members.data(), n, &bad);
+  } catch (const HipError& e) {
+    blame(e.msg);
+    return SFFGPU_ERR_HIP;
+  } catch (const std::exception& e) {
+    blame(e.what());
+    return SFFGPU_ERR_STATE;
+  }
+  return SFFGPU_OK;
+}
+static int smooth_ready(sffgpu_forest* f) {
+  if (!f->f->nm.empty()) return SFFGPU_OK;
+  f->owner->c->err = "smooth_paths: call sffgpu_forest_paths first";
+  return SFFGPU_ERR_STATE;
+}
+static int smooth_ready(sffgpu_rrt* r) {
+  try { r->r->batch_sync_host(); } catch (const HipError& e) { r->owner->c->err = e.msg; return SFFGPU_ERR_HIP; }
+  if (!r->r->nm.empty()) return SFFGPU_OK;
+  r->owner->c->err = "rrt smooth_paths: call sffgpu_rrt_paths first";
+  return SFFGPU_ERR_STATE;
+}
+static void copy_dist(Forest& F, double* dist) {
+  for (int i = 0; i < F.num_roots; ++i)
+    for (int j = 0; j < F.num_roots; ++j) dist[(size_t)i * F.num_roots + j] = i == j ? 0.0 : F.NM(i, j).dist;
+}
+
 extern "C" {
 
 const char* sffgpu_version(void) { return "sffgpu 0.1 (gfx950)"; }
@@ -305,11 +359,26 @@ int sffgpu_forest_smooth_paths(sffgpu_forest* f, double* dist) {
   if (!f || !dist) return SFFGPU_ERR_ARG;
   Forest& F = *f->f;
   if (F.nm.empty()) { f->owner->c->err = "smooth_paths: call sffgpu_forest_paths first"; return SFFGPU_ERR_STATE; }
+  if (F.kn.smooth_loop) {   // (SFFGPU_SMOOTH_LOOP=1 at the forest's creation: the device loop, a batch of one)
+    double* one[1] = {dist};
+    return sffgpu_forest_smooth_paths_batch(&f, 1, one, nullptr);
+  }
   GUARD(f->owner, {
     F.smooth_paths();
     for (int i = 0; i < F.num_roots; ++i)
       for (int j = 0; j < F.num_roots; ++j) dist[(size_t)i * F.num_roots + j] = i == j ? 0.0 : F.NM(i, j).dist;
   });
+}
+int sffgpu_forest_smooth_paths_batch(sffgpu_forest* const* f, int n, double* const* dist, int32_t* failed) {
+  const int rc = smooth_batch_entry(f, n, failed, [](sffgpu_forest* h) { return smooth_ready(h); });
+  if (rc == SFFGPU_OK && dist)
+    for (int i = 0; i < n; ++i) if (dist[i]) copy_dist(*f[i]->f, dist[i]);
+  return rc;
+}
+int sffgpu_forest_get_smooth_stats(sffgpu_forest* f, sffgpu_smooth_stats* out) {
+  if (!f || !out) return SFFGPU_ERR_ARG;
+  *out = f->f->sm;
+  return SFFGPU_OK;
 }
 int sffgpu_forest_path_plan(sffgpu_forest* f, int i, int j, int32_t* node_ids, int cap) {
   if (!f || i < 0 || j < 0 || i >= f->f->num_roots || j >= f->f->num_roots) return SFFGPU_ERR_ARG;
@@ -437,6 +506,10 @@ int sffgpu_rrt_smooth_paths(sffgpu_rrt* r) {
   RRT_SYNC(r);
   Rrt& R = *r->r;
   if (R.nm.empty()) { r->owner->c->err = "rrt smooth_paths: call sffgpu_rrt_paths first"; return SFFGPU_ERR_STATE; }
+  if (R.kn.smooth_loop) {   // (SFFGPU_SMOOTH_LOOP=1 at the session's creation: the device loop, a batch of one)
+    const int rc = sffgpu_rrt_smooth_paths_batch(&r, 1, nullptr);
+    return rc == SFFGPU_OK ? (int)R.link_plans.size() : rc;
+  }
   try {
     R.smooth_paths();
   } catch (const HipError& e) {
@@ -444,6 +517,14 @@ int sffgpu_rrt_smooth_paths(sffgpu_rrt* r) {
     return SFFGPU_ERR_HIP;
   }
   return (int)R.link_plans.size();
+}
+int sffgpu_rrt_smooth_paths_batch(sffgpu_rrt* const* r, int n, int32_t* failed) {
+  return smooth_batch_entry(r, n, failed, [](sffgpu_rrt* h) { return smooth_ready(h); });
+}
+int sffgpu_rrt_get_smooth_stats(sffgpu_rrt* r, sffgpu_smooth_stats* out) {
+  if (!r || !out) return SFFGPU_ERR_ARG;
+  *out = r->r->sm;
+  return SFFGPU_OK;
 }
 int sffgpu_rrt_link_plan(sffgpu_rrt* r, int k, int32_t* node_ids, int cap) {
   if (!r) return SFFGPU_ERR_ARG;

@@ -254,11 +254,11 @@ Ctx::~Ctx() {
                     &d_a, &d_b, &d_c, &d_d, &d_e, &d_f, &d_g, &d_h, &r_in, &r_out, &r_out2, &r_q, &r_cnt, &r_hidx,
                     &r_hdist, &r_sega, &r_segb, &r_items, &r_items2, &r_center, &r_qrec, &env_clear, &env_clear_edge, &env_cand, &g_cnt, &g_items, &g_ovfcnt, &g_ovf, &t_cnt, &t_items, &t_ovfcnt, &t_ovf, &t_occ, &g_lite, &g_ovf_lite, &t_lite, &t_ovf_lite, &env_tg_start, &env_tg_list, &r_sub, &env_ext, &rr_q1, &rr_q2, &rr_a, &rr_out, &rr_sq, &rr_np, &rr_alt, &rr_q2b, &rr_sqb, &seg_job[0].ids, &seg_job[0].a, &seg_job[0].b, &seg_job[0].c, &seg_job[1].ids, &seg_job[1].a,
                     &seg_job[1].b, &seg_job[1].c, &seg_job[2].ids, &seg_job[2].a, &seg_job[2].b, &seg_job[2].c, &seg_job[3].ids, &seg_job[3].a,
-                    &seg_job[3].b, &seg_job[3].c};
+                    &seg_job[3].b, &seg_job[3].c, &sm_dev};
   for (DevBuf* b : bufs) b->release();
   for (auto& b : level_box) b.release();
   PinBuf* pins[] = {&h_a, &h_b, &h_c, &h_d, &h_e, &h_f, &h_g, &h_h, &p_in, &p_out, &rr_hq, &rr_hout, &seg_job[0].hids, &seg_job[0].hc, &seg_job[1].hids, &seg_job[1].hc, &seg_job[2].hids, &seg_job[2].hc,
-                    &seg_job[3].hids, &seg_job[3].hc};
+                    &seg_job[3].hids, &seg_job[3].hc, &sm_pin};
   for (PinBuf* b : pins) b->release();
   if (copy_stream) (void)hipStreamDestroy(copy_stream);
   if (own_stream) (void)hipStreamDestroy(own_stream);

@@ -6,6 +6,7 @@
 #include <string.h>
 
 #include <algorithm>
+#include <functional>
 #include <map>
 #include <unordered_set>
 #include <string>
@@ -173,6 +174,8 @@ struct Ctx {
   // scratch
   DevBuf d_a, d_b, d_c, d_d, d_e, d_f, d_g, d_h;
   PinBuf h_a, h_b, h_c, h_d, h_e, h_f, h_g, h_h;
+  DevBuf sm_dev;   // path smoothing on the device (smooth_batch.cpp): path table | control blocks | output rows | positions,
+  PinBuf sm_pin;   // of the call whose first member this context belongs to, and their pinned image
   // round pipeline buffers of the forest engine (kept apart from the batch entry points' scratch)
   DevBuf r_in, r_out, r_q, r_cnt, r_hidx, r_hdist, r_sega, r_segb, r_items, r_items2, r_sub, r_center;
   DevBuf r_qrec;   // per sample: QRec (kernels.h), written by the sampling kernels for k_query_block
@@ -526,6 +529,7 @@ struct Forest {
   void get_paths();
   void get_all_paths();
   void smooth_paths();   // src/forest.h:464-511, edge checks batched on the GPU
+  sffgpu_smooth_stats sm{};   // what the device loop (smooth_batch.cpp) has done for this forest; all zero = it never ran
 
   Forest(Ctx* c, const sffgpu_forest_cfg& cf, const double* roots6, int n_roots);
   int add_node(const double* pos, int tree, int parent, double dclosest, double droot, unsigned it);
@@ -599,6 +603,7 @@ struct Rrt {
   void get_paths();
   std::vector<std::vector<int>> link_plans;   // plans of the central tree's links (what smoothPaths works on)
   void smooth_paths();                        // src/rrt.h:354-379, edge checks batched on the GPU
+  sffgpu_smooth_stats sm{};                   // what the device loop (smooth_batch.cpp) has done for this session
   std::vector<double> pend_pos;       // accepted nodes of the current wave not yet in the device store
   std::vector<int32_t> pend_tree;
   bool defer_append = false;
@@ -638,5 +643,26 @@ struct Rrt {
 // session only when it was created under SFFGPU_LAZY_BATCH=1; distinct contexts, one device).  A member that throws ends the call: *failed = its index, the
 // exception goes on to the caller; every other member has been taken in after a whole number of launches.
 void run_rrt_batch(Rrt* const* members, int n, int max_iterations, int* failed);
+
+// Path smoothing on the device (smooth_batch.cpp): smoothPaths' walk for every path of n planners in one launch of
+// k_smooth_paths, one wavefront per path, launched again until every path is done (a launch tests at most max_edges edges
+// per path).  One runner for forests and RRT sessions: a member is an adapter - its context, its plans, where a node's
+// position lies in its host mirror, and what to do with the chosen t of every step of a path (Forest: drop the entries and
+// replay the fp64 cost arithmetic of paths.cpp; Rrt: drop the entries).  The caller has checked the members (paths extracted,
+// one device).  Nothing of a planner is touched before every path of every member is decided: a member that throws ends the
+// call with *failed = its index and every member as it was.
+struct SmoothMember {
+  Ctx* ctx;
+  int max_edges;                                   // Knobs::smooth_edges of the planner
+  sffgpu_smooth_stats* stats;
+  uint64_t* path_free_calls;                       // the planner's reference-equivalent counters
+  uint64_t* collide_calls;
+  std::vector<std::vector<int>*> plans;            // every path, in the order the host walk takes them
+  std::function<const double*(int)> pos;           // node id -> its fp64 pos[6]
+  std::function<void(int, const int32_t*, int)> apply;   // (path, the chosen t of its steps, how many)
+};
+void run_smooth_batch(SmoothMember* members, int n, int* failed);
+SmoothMember smooth_member(Forest& f);
+SmoothMember smooth_member(Rrt& r);
 
 }  // namespace sff

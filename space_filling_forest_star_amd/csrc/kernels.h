@@ -741,6 +741,31 @@ struct RrtSeqArgs {
 // largest collide_lds_bytes(rob.n_tri, 1) among them.  Returns the first error of setting the kernel's attribute or of the
 // launch itself.
 hipError_t launch_rrt_seq_batch(hipStream_t s, const RrtSeqArgs* members_dev, int n, bool optimize, bool lazy, size_t lds);
+// ---- Path smoothing (k_smooth_paths, smooth_paths.inc): smoothPaths' walk (src/forest.h:464-511, src/rrt.h:354-379) over
+// the paths of many planners in one launch, workgroup b = one wavefront = paths_dev[b].  A path is `len` fp64 positions (the
+// plan's own, gathered by the host).  Step: far end g, candidates t = 0 .. g-2 in ascending order, isPathFree(pos[t], pos[g])
+// until the first free one; the chosen t (g-1 when none was free) goes to out[n_out++] and becomes the next g.  Entries
+// behind t are never looked at again, so the walk runs on the ORIGINAL indices and the host drops the entries afterwards.
+// A launch tests at most max_edges edges of a path and leaves the path where the next launch continues (g, t_next).
+struct SmoothCtrl {                  // control / status block of one path (HBM; copied back after every launch)
+  int32_t g, t_next;                 // the step's far end (<= 0: the path is done) and the candidate its walk tests next
+  int32_t n_out, status;             // steps decided so far; SFFK_SMOOTH_* below
+  unsigned long long collide_calls, path_free_calls;   // reference-equivalent counters (they follow the early stop)
+  unsigned long long segments, samples;                 // what the wavefront ran
+};
+#define SFFK_SMOOTH_RAN 0            // done (g <= 0), or the launch's edge budget ran out
+#define SFFK_SMOOTH_HOST 1           // the edge (t_next, g) could not be decided here: the host finishes this step
+struct SmoothPathArgs {
+  SmoothCtrl* ctrl;
+  const double* pos;                 // len x 6
+  int32_t* out;                      // the chosen t of every step (at most len - 1)
+  EnvView env;
+  RobotView rob;
+  int len, max_edges;
+};
+// lds = the largest collide_lds_bytes(rob.n_tri, 1) among the paths' members.  Returns the first error of setting the
+// kernel's attribute or of the launch itself.
+hipError_t launch_smooth_paths(hipStream_t s, const SmoothPathArgs* paths_dev, int n, size_t lds);
 // the transcendental values of n engine words (3 doubles per word: cos, sin of the word as an angle, acos of it as the pitch draw)
 void launch_ring_trig(hipStream_t s, const uint64_t* words, double* trig, int n);
 // multi-GPU: the answer record of one sample as it travels in the all-gather of a round:

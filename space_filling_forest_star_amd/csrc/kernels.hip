@@ -4440,6 +4440,7 @@ hipError_t launch_seq_waves_batch(hipStream_t s, const SeqArgs* members_dev, int
 }
 
 #include "rrt_seq_batch.inc"
+#include "smooth_paths.inc"
 
 template <bool OPT, bool PRIO, bool GOAL>
 static void launch_seq_waves_as(hipStream_t s, const SeqArgs& a, size_t lds) {

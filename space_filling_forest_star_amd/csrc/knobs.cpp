@@ -100,6 +100,9 @@ Knobs Knobs::from_env() {
   k.rrt_no_grid = is_set("SFFGPU_RRT_NO_GRID");
   k.rrt_no_chain_conn = is_set("SFFGPU_RRT_NO_CHAIN_CONN");
   k.lazy_batch = flag("SFFGPU_LAZY_BATCH", k.lazy_batch);
+
+  k.smooth_loop = flag("SFFGPU_SMOOTH_LOOP", k.smooth_loop);
+  k.smooth_edges = int_in("SFFGPU_SMOOTH_EDGES", k.smooth_edges, 1);
   return k;
 }
 

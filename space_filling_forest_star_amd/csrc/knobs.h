@@ -93,6 +93,11 @@ struct Knobs {
   bool lazy_batch = false;          // SFFGPU_LAZY_BATCH=1: a lazy_edge session (LazyTSP::runRRT, src/lazy.h:160-284) may be a member of a session batch
                                     // (k_rrt_seq_batch<., true>); 0 = a batch refuses it
 
+  // ---- path smoothing (forests and RRT sessions)
+  bool smooth_loop = false;         // SFFGPU_SMOOTH_LOOP=1: sffgpu_forest_smooth_paths / sffgpu_rrt_smooth_paths of a planner created under it walk the
+                                    // paths on the device (k_smooth_paths, the batch runner with one member); 0 = the host walk, one edge batch per step
+  int smooth_edges = 64;            // SFFGPU_SMOOTH_EDGES (>= 1): most edges one launch of k_smooth_paths tests per path before the host launches again
+
   static Knobs from_env();
 };
 
