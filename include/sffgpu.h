@@ -37,6 +37,39 @@ const char* sffgpu_last_error(sffgpu_ctx* ctx); /* ctx may be NULL: last create(
  * src/environment.h:306-316).  The ENV model may be empty (HasMap == false). */
 int sffgpu_mesh_upload(sffgpu_ctx* ctx, int role, const double* tri9, int n_tri);
 
+/* Member contexts: a new context on `owner`'s device that uses owner's ENV and ROBOT models as they are at this moment -
+ * nothing is uploaded, built or copied, and the call waits for nothing.  What a batch of N planners needs (one context per
+ * member, a context owns one node store) without N copies of the world: apart from the models the new context is a full
+ * context - its own streams, node store, grids, scratch and error string - and everything that takes a context takes it.
+ * `owner` may itself be a member: the new context then holds the same models.  Contexts may be destroyed in any order, a
+ * member outlives its owner; the models' device memory goes with the last context that holds them.
+ * SFFGPU_ERR_ARG: a NULL argument.  SFFGPU_ERR_STATE, with a message on `owner`: owner has not had BOTH meshes uploaded.
+ * While more than one live context holds the same models, sffgpu_mesh_upload on ANY of them - owner or member - returns
+ * SFFGPU_ERR_STATE and leaves everything as it was (there is no copy-on-write: the others' kernels read those buffers);
+ * once the other holders are destroyed, the upload works again.
+ * The member reads the SFFGPU_* environment at this call like sffgpu_create does; the knobs that shaped the models
+ * (SFFGPU_NO_CLEARANCE, SFFGPU_CLEAR_CELLS, SFFGPU_CLEAR_HDIV, SFFGPU_NO_TRIGRID, SFFGPU_TG_DIV, SFFGPU_NO_CAND) stay as
+ * they were when the models were built.
+ * A member context carries no round grid - the second node grid of the engines that evaluate a wave of many slots in
+ * rounds - until something needs one: a forest with wave > 1, a wave the one-wavefront loops hand to the host-replay
+ * engine, the multi-GPU round protocol.  It is then allocated at once, on the host, before the first launch that reads
+ * it.  Forest batches, session batches and device smoothing never do. */
+int sffgpu_create_member(sffgpu_ctx* owner, sffgpu_ctx** out);
+
+/* Device memory held by the context's own buffers, in bytes, as sums of their capacities.  Buffers that forests and
+ * sessions own themselves (device engine state, engine-word rings, session blocks) are not counted. */
+typedef struct {
+  uint64_t env_bytes;        /* the collision models; 0 for every holder but the context that built them */
+  uint64_t env_holders;      /* live contexts that hold these models (1 = not shared) */
+  uint64_t store_bytes;      /* node store */
+  uint64_t grid_bytes;       /* node grid and both overflow counters */
+  uint64_t round_grid_bytes; /* the round grid's cells, buckets, overflow lists and occupancy bits (0 on a member
+                                context until a round engine has asked for it) */
+  uint64_t other_bytes;      /* scratch, round pipeline, RRT chain, smoothing */
+  uint64_t total_bytes;
+} sffgpu_ctx_memory;
+int sffgpu_ctx_get_memory(sffgpu_ctx* ctx, sffgpu_ctx_memory* out);
+
 /* Poses.  Wherever the caller hands in poses (x y z yaw pitch roll) - sffgpu_collide_poses, sffgpu_collide_segments, the
  * centres of sffgpu_sample_steer, the roots and the goal of sffgpu_forest_create / sffgpu_rrt_create - every coordinate
  * must be finite and every angle must lie within +-2^20 * pi/2 (about 1.647e6; SFFP_TRIG_DOMAIN of csrc/sff_pmath.h),
@@ -182,7 +215,8 @@ int sffgpu_forest_run(sffgpu_forest* f, int max_waves);
  * with SFFGPU_PRIO_GOAL_LOOP=1 - that knob alone, the other two do not cover it (all three default 0: the member is
  * refused).  A goal member ends at the iteration that reaches its goal, like sffgpu_forest_run.  The kinds of one batch
  * (SFF / SFF*; plain, priority frontier, single goal, priority + goal) go out as up to eight launches.  All members on one
- * device, each on a context of its own (a context owns one node store).
+ * device, each on a context of its own (a context owns one node store; sffgpu_create_member makes them from one context
+ * that has the world, without uploading it again).
  * SFFGPU_ERR_ARG, before anything has run: a member that does not qualify, two members of one context, the same forest
  * twice, n <= 0, f == NULL.  When a member fails, its error code is returned, *failed is its index (-1 otherwise) and
  * the message is on ITS context; every other member has been left after a whole number of launches - consistent, and

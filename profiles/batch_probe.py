@@ -14,6 +14,13 @@ seeds; the clock is the host's, around calls that end in a synchronisation.  App
 
   python profiles/batch_probe.py --parent-lib /path/to/parent/libsffgpu.so [--kinds sff,star] [--repeats 3]
   python profiles/batch_probe.py --parent-lib ... --legs a --a-builds new,parent --batch-sizes 64    (one build against another)
+  python profiles/batch_probe.py --parent-lib ... --legs a --a-builds new,parent --batch-sizes 64,128 --share-env
+      (member contexts: on THIS build context 0 uploads and the others are made with sffgpu_create_member; a parent build,
+       which has no such entry point, sets every context up in full as before)
+
+Every record of leg a also carries the set-up: setup_seconds = the wall time of the contexts (first sffgpu_create to the
+last context ready) + that of creating the measured forests, and - a build that has sffgpu_ctx_get_memory - memory_member_1,
+Context.memory() of member 1 after the run.
 """
 import argparse
 import ctypes as C
@@ -41,29 +48,39 @@ def child(a):
     import space_filling_forest_star_amd as S
     sc = common.scenario("dense3d")
     n_ctx = a.B if a.leg == "a" else 1
+    t_setup = time.perf_counter()
     ctx0 = S.Context(0)
     ctx0.upload_env(sc["env"])
     ctx0.upload_robot(sc["robot"])
+    setup_ctx = time.perf_counter() - t_setup
     roots = common.free_roots(lambda p: int(ctx0.collide_poses(p[None, :])[0]), sc["limits"], 10, seed=1)
     mem0 = free_bytes()
     ctxs = [ctx0]
+    t_setup = time.perf_counter()
     for _ in range(n_ctx - 1):
-        c = S.Context(0)
-        c.upload_env(sc["env"])
-        c.upload_robot(sc["robot"])
+        if a.share_env:
+            c = ctx0.member()
+        else:
+            c = S.Context(0)
+            c.upload_env(sc["env"])
+            c.upload_robot(sc["robot"])
         ctxs.append(c)
+    setup_ctx += time.perf_counter() - t_setup
 
     def forest(ctx, seed, budget):
         return S.Forest(ctx, roots, sc["limits"], dist_tree=sc["dist_tree"], sampling_dist=sc["sampling_dist"], dim=6,
                         max_iterations=2 ** 31 - 1, node_budget=budget, wave=1, seed=seed, optimize=bool(a.optimize))
 
     stats, fps = [], []
+    setup_forests = None
     if a.leg == "a":
         warm = [forest(c, 1000 + i, 1500) for i, c in enumerate(ctxs)]
         S.run_batch(warm)
         for f in warm:
             f.close()
+        t = time.perf_counter()
         fs = [forest(c, 1 + i, a.budget) for i, c in enumerate(ctxs)]
+        setup_forests = time.perf_counter() - t
         t = time.perf_counter()
         S.run_batch(fs)
         dt = time.perf_counter() - t
@@ -93,6 +110,9 @@ def child(a):
         "host_share": (sum(s["host_ms"] for s in stats) / max(1e-9, sum(s["total_ms"] for s in stats))),
         "device_bytes_per_member": (mem0 - mem1) / max(1, n_ctx - 1) if n_ctx > 1 else None,
         "device_bytes_first_member_forest": (mem0 - mem1) if n_ctx == 1 else None,
+        "share_env": bool(a.share_env), "setup_contexts_seconds": setup_ctx, "setup_forests_seconds": setup_forests,
+        "setup_seconds": None if setup_forests is None else setup_ctx + setup_forests,
+        "memory_member_1": ctxs[1].memory() if n_ctx > 1 and hasattr(S.lib(), "sffgpu_ctx_get_memory") else None,
         "fingerprints": ["%016x" % x for x in fps]}), flush=True)
 
 
@@ -115,6 +135,7 @@ def main():
     ap.add_argument("--c-size", type=int, default=8)  # leg c
     ap.add_argument("--legs", default="a,b,c")
     ap.add_argument("--a-builds", default="new")      # leg a; "new,parent": the parent's run_batch too (a parent that has one)
+    ap.add_argument("--share-env", action="store_true")   # leg a, this build: contexts 1.. are members of context 0
     ap.add_argument("--child-timeout", type=int, default=420)
     ap.add_argument("--out", default=OUT)
     a = ap.parse_args()
@@ -142,6 +163,8 @@ def main():
                     env["SFFGPU_SPEC"] = "0"
                 cmd = [sys.executable, os.path.abspath(__file__), "--child", "--leg", leg, "--build", build, "--B", str(B),
                        "--optimize", str(opt), "--repeat", str(rep), "--budget", str(a.budget)]
+                if a.share_env and leg == "a" and build == "new":
+                    cmd.append("--share-env")
                 p = subprocess.run(cmd, env=env, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True, timeout=a.child_timeout)
                 lines = [ln for ln in p.stdout.splitlines() if ln.startswith("RESULT ")]
                 if p.returncode != 0 or not lines:
@@ -153,6 +176,10 @@ def main():
                 print("%-4s leg %s %-6s B %3d rep %d: %7.3f s  %9.0f it/s  %8.0f nodes/s  launches %d  host share %.3f" % (
                     rec["kind"], leg, build, B, rep, rec["seconds"], rec["iterations_per_s"], rec["nodes_per_s"], rec["launches"],
                     rec["host_share"]), flush=True)
+                if leg == "a" and B > 1:
+                    print("     set-up %.2f s (contexts %.2f, forests %.2f)  device memory per member %.3f GB%s" % (
+                        rec["setup_seconds"], rec["setup_contexts_seconds"], rec["setup_forests_seconds"],
+                        rec["device_bytes_per_member"] / 1e9, "  (members of context 0)" if rec["share_env"] else ""), flush=True)
 
 
 if __name__ == "__main__":

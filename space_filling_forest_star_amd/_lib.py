@@ -26,6 +26,7 @@ EXPORTED_SYMBOLS = [
     "sffgpu_forest_run_batch", "sffgpu_rrt_run_batch",
     "sffgpu_forest_smooth_paths_batch", "sffgpu_rrt_smooth_paths_batch", "sffgpu_forest_get_smooth_stats",
     "sffgpu_rrt_get_smooth_stats",
+    "sffgpu_create_member", "sffgpu_ctx_get_memory",
 ]
 
 # sffgpu_allgather_fn: int fn(void* user, const void* send_dev, void* recv_dev, size_t words_i32, void* hip_stream)
@@ -90,6 +91,16 @@ class SmoothStats(C.Structure):
     """sffgpu_smooth_stats: what the device loop of path smoothing (k_smooth_paths) has done for one planner"""
     _fields_ = [("launches", C.c_uint64), ("paths", C.c_uint64), ("steps", C.c_uint64), ("edges", C.c_uint64),
                 ("host_edges", C.c_uint64), ("ms", C.c_double)]
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_}
+
+
+class CtxMemory(C.Structure):
+    """sffgpu_ctx_memory: device memory held by a context's own buffers (bytes, sums of capacities)"""
+    _fields_ = [("env_bytes", C.c_uint64), ("env_holders", C.c_uint64), ("store_bytes", C.c_uint64),
+                ("grid_bytes", C.c_uint64), ("round_grid_bytes", C.c_uint64), ("other_bytes", C.c_uint64),
+                ("total_bytes", C.c_uint64)]
 
     def as_dict(self):
         return {k: getattr(self, k) for k, _ in self._fields_}
@@ -193,6 +204,9 @@ def lib():
     L.sffgpu_forest_round_begin.argtypes = [C.c_void_p, c_ip, c_ip]
     L.sffgpu_forest_round_records.argtypes = [C.c_void_p, c_ip, C.c_int]
     L.sffgpu_forest_round_commit.argtypes = [C.c_void_p, c_ip, C.c_int, c_ip, C.c_int]
+    if hasattr(L, "sffgpu_create_member"):   # (SFFGPU_LIB may name a build from before member contexts; member() says so)
+        L.sffgpu_create_member.argtypes = [C.c_void_p, C.POINTER(C.c_void_p)]
+        L.sffgpu_ctx_get_memory.argtypes = [C.c_void_p, C.POINTER(CtxMemory)]
     _LIB = L
     return L
 
@@ -226,6 +240,27 @@ class Context:
         if rc != 0:
             raise SffGpuError("sffgpu_create failed: %s" % self._L.sffgpu_last_error(None).decode())
         self.h = h
+
+    def member(self):
+        """A new Context on this one's device that uses its ENV and ROBOT models as they are now (sffgpu_create_member):
+        nothing is uploaded or built again.  The two are independent afterwards - close them in any order; while both
+        live, upload_env / upload_robot on either raises."""
+        if not hasattr(self._L, "sffgpu_create_member"):
+            raise SffGpuError("this build of libsffgpu has no sffgpu_create_member")
+        h = C.c_void_p()
+        self._chk(self._L.sffgpu_create_member(self.h, C.byref(h)))
+        m = Context.__new__(Context)   # (holds no reference to this context: the library keeps the models alive)
+        m._L = self._L
+        m.h = h
+        return m
+
+    def memory(self):
+        """device memory of this context's own buffers in bytes: the fields of sffgpu_ctx_memory"""
+        if not hasattr(self._L, "sffgpu_ctx_get_memory"):
+            raise SffGpuError("this build of libsffgpu has no sffgpu_ctx_get_memory")
+        m = CtxMemory()
+        self._chk(self._L.sffgpu_ctx_get_memory(self.h, C.byref(m)))
+        return m.as_dict()
 
     def close(self):
         if getattr(self, "h", None):

@@ -169,6 +169,29 @@ int sffgpu_create(int device, sffgpu_ctx** out) {
   }
 }
 
+int sffgpu_create_member(sffgpu_ctx* owner, sffgpu_ctx** out) {
+  if (out) *out = nullptr;
+  if (!owner || !out) return SFFGPU_ERR_ARG;
+  if (!owner->c->have_env() || !owner->c->have_robot()) {
+    owner->c->err = "create_member: upload ENV and ROBOT meshes to the owner first";
+    return SFFGPU_ERR_STATE;
+  }
+  try {
+    Ctx* c = new Ctx(owner->c->device, owner->c);
+    *out = new sffgpu_ctx{c};
+    return SFFGPU_OK;
+  } catch (const HipError& e) {
+    owner->c->err = e.msg;
+    return SFFGPU_ERR_HIP;
+  }
+}
+
+int sffgpu_ctx_get_memory(sffgpu_ctx* ctx, sffgpu_ctx_memory* out) {
+  if (!ctx || !out) return SFFGPU_ERR_ARG;
+  ctx->c->memory(out);
+  return SFFGPU_OK;
+}
+
 void sffgpu_destroy(sffgpu_ctx* ctx) {
   if (!ctx) return;
   delete ctx->c;

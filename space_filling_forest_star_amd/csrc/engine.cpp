@@ -8,6 +8,7 @@
 #include <cstdlib>
 #include <cstring>
 #include <limits>
+#include <stdexcept>
 
 #include "sff_geom.h"
 
@@ -150,7 +151,7 @@ int Mt64::uniform_int(int lo, int hi) {
 }
 
 // ------------------------------------------------------------------ context
-Ctx::Ctx(int dev) : device(dev) {
+Ctx::Ctx(int dev, const Ctx* owner) : device(dev) {
   kn = Knobs::from_env();
   int n = 0;
   HIPCHK(hipGetDeviceCount(&n));
@@ -161,6 +162,16 @@ Ctx::Ctx(int dev) : device(dev) {
   HIPCHK(hipGetDeviceProperties(&prop, dev));
   if (std::string(prop.gcnArchName).find("gfx950") == std::string::npos)
     throw HipError{std::string("device is ") + prop.gcnArchName + ", kernels are built for gfx950 only"};
+  // (the block only once the device is known to be good: its destructor selects the device it was made for)
+  if (owner) {   // a member: the owner's models as they are (nothing of them is written again while two contexts hold them)
+    env = owner->env;
+    envv = owner->envv;
+    robv = owner->robv;
+    env_built_here = false;
+    round_lazy = true;
+  } else {
+    env = std::make_shared<EnvBlock>(dev);
+  }
   {
     int khz = 0;
     if (hipDeviceGetAttribute(&khz, hipDeviceAttributeWallClockRate, dev) == hipSuccess && khz > 0) wall_clock_khz = khz;
@@ -250,13 +261,13 @@ Ctx::~Ctx() {
   if (ev_early) (void)hipEventDestroy(ev_early);
   for (auto& t : pending) { (void)hipEventDestroy(t.a); (void)hipEventDestroy(t.b); }
   for (auto e : pool) (void)hipEventDestroy(e);
-  DevBuf* bufs[] = {&env_tri, &env_box, &env_plane, &rob_tri, &sx, &sy, &sz, &syaw, &spitch, &sroll, &stree, &spos,
+  DevBuf* bufs[] = {&sx, &sy, &sz, &syaw, &spitch, &sroll, &stree, &spos,
                     &d_a, &d_b, &d_c, &d_d, &d_e, &d_f, &d_g, &d_h, &r_in, &r_out, &r_out2, &r_q, &r_cnt, &r_hidx,
-                    &r_hdist, &r_sega, &r_segb, &r_items, &r_items2, &r_center, &r_qrec, &env_clear, &env_clear_edge, &env_cand, &g_cnt, &g_items, &g_ovfcnt, &g_ovf, &t_cnt, &t_items, &t_ovfcnt, &t_ovf, &t_occ, &g_lite, &g_ovf_lite, &t_lite, &t_ovf_lite, &env_tg_start, &env_tg_list, &r_sub, &env_ext, &rr_q1, &rr_q2, &rr_a, &rr_out, &rr_sq, &rr_np, &rr_alt, &rr_q2b, &rr_sqb, &seg_job[0].ids, &seg_job[0].a, &seg_job[0].b, &seg_job[0].c, &seg_job[1].ids, &seg_job[1].a,
+                    &r_hdist, &r_sega, &r_segb, &r_items, &r_items2, &r_center, &r_qrec, &g_cnt, &g_items, &g_ovfcnt, &g_ovf, &t_cnt, &t_items, &t_ovfcnt, &t_ovf, &t_occ, &g_lite, &g_ovf_lite, &t_lite, &t_ovf_lite, &r_sub, &rr_q1, &rr_q2, &rr_a, &rr_out, &rr_sq, &rr_np, &rr_alt, &rr_q2b, &rr_sqb, &seg_job[0].ids, &seg_job[0].a, &seg_job[0].b, &seg_job[0].c, &seg_job[1].ids, &seg_job[1].a,
                     &seg_job[1].b, &seg_job[1].c, &seg_job[2].ids, &seg_job[2].a, &seg_job[2].b, &seg_job[2].c, &seg_job[3].ids, &seg_job[3].a,
                     &seg_job[3].b, &seg_job[3].c, &sm_dev};
   for (DevBuf* b : bufs) b->release();
-  for (auto& b : level_box) b.release();
+  env.reset();   // (the models go with their last holder)
   PinBuf* pins[] = {&h_a, &h_b, &h_c, &h_d, &h_e, &h_f, &h_g, &h_h, &p_in, &p_out, &rr_hq, &rr_hout, &seg_job[0].hids, &seg_job[0].hc, &seg_job[1].hids, &seg_job[1].hc, &seg_job[2].hids, &seg_job[2].hc,
                     &seg_job[3].hids, &seg_job[3].hc, &sm_pin};
   for (PinBuf* b : pins) b->release();
@@ -329,8 +340,33 @@ static inline uint64_t spread21(uint64_t v) {
 // triangles are ordered along a Morton curve of their box centres, 64 consecutive triangles
 // form a level-0 group, 64 consecutive groups a level-1 group, and so on until <= 64 remain.
 void Ctx::upload_mesh(int role, const double* tri9, int n) {
+  // (no copy-on-write: the other holders' kernels read these buffers)
+  if (env.use_count() > 1)
+    throw std::runtime_error("mesh_upload: the models of this context are shared with " + std::to_string(env.use_count() - 1) +
+                             " other live context(s) (sffgpu_create_member); destroy them first");
   kn = Knobs::from_env();
   HIPCHK(hipSetDevice(device));
+  struct Views {   // this context's copies follow the block, whatever the upload throws
+    Ctx& c;
+    ~Views() { c.envv = c.env->envv; c.robv = c.env->robv; }
+  } views{*this};
+  env->upload(kn, stream, role, tri9, n);
+}
+
+EnvBlock::~EnvBlock() {
+  (void)hipSetDevice(device);
+  DevBuf* bufs[] = {&env_tri, &env_box, &env_plane, &rob_tri, &env_clear, &env_clear_edge, &env_ext, &env_cand, &env_tg_start, &env_tg_list};
+  for (DevBuf* b : bufs) b->release();
+  for (auto& b : level_box) b.release();
+}
+size_t EnvBlock::device_bytes() const {
+  size_t sum = env_tri.cap + env_box.cap + env_plane.cap + rob_tri.cap + env_clear.cap + env_clear_edge.cap + env_ext.cap + env_cand.cap +
+               env_tg_start.cap + env_tg_list.cap;
+  for (const DevBuf& b : level_box) sum += b.cap;
+  return sum;
+}
+
+void EnvBlock::upload(const Knobs& kn, hipStream_t stream, int role, const double* tri9, int n) {
   if (role == SFFGPU_MESH_ROBOT) {
     if (n <= 0) throw HipError{"robot mesh must have at least one triangle"};
     rob_tri.ensure((size_t)n * 9 * sizeof(double));
@@ -353,9 +389,9 @@ void Ctx::upload_mesh(int role, const double* tri9, int n) {
     robv.radius = rad;
     have_robot = true;
     h_rob.assign(tri9, tri9 + (size_t)n * 9);
-    build_robot_extents();
-    build_clearance();
-    build_tri_grid();
+    build_robot_extents(kn);
+    build_clearance(kn, stream);
+    build_tri_grid(kn, stream);
     return;
   }
   if (role != SFFGPU_MESH_ENV) throw HipError{"unknown mesh role"};
@@ -443,15 +479,15 @@ void Ctx::upload_mesh(int role, const double* tri9, int n) {
     if (groups <= 64) break;
   }
   envv.n_levels = L;
-  build_robot_extents();
-  build_clearance();
-  build_tri_grid();
+  build_robot_extents(kn);
+  build_clearance(kn, stream);
+  build_tri_grid(kn, stream);
 }
 
 // Extent of the un-rotated robot along every environment triangle's normal (kernels.h, EnvView::tri_ext): edge samples
 // carry no rotation (src/problemStruct.h:157-165), so "the whole robot on one side of the triangle's plane" is one
 // comparison per (sample, triangle) in the exact kernel.
-void Ctx::build_robot_extents() {
+void EnvBlock::build_robot_extents(const Knobs& kn) {
   envv.tri_ext = nullptr;
   envv.cand = nullptr;
   if (!have_env || !have_robot || envv.n_tri <= 0 || h_rob.empty() || h_plane.size() != (size_t)envv.n_tri * 5) return;
@@ -492,7 +528,7 @@ void Ctx::build_robot_extents() {
 // Clearance bits over the environment box (kernels.h, EnvView): one bit per cell, set when a robot whose
 // bounding-sphere centre lies anywhere in the cell cannot touch a triangle.  The cell edge follows the
 // robot radius but the grid is capped at 2^27 cells (16 MB of bits) and by the build cost.
-void Ctx::build_clearance() {
+void EnvBlock::build_clearance(const Knobs& kn, hipStream_t stream) {
   envv.clear_bits = nullptr;
   envv.clear_bits_edge = nullptr;
   clear_cells = 0;
@@ -577,7 +613,7 @@ void Ctx::build_clearance() {
 // Triangle grid over the environment's box (kernels.h, EnvView): cell edge = a third of the largest query box the
 // collision kernels ask with (robot extent + one 64-sample chunk of an edge, 6.4 units), but at most 128 cells per
 // axis.  Built on the device in two passes around a host prefix sum.
-void Ctx::build_tri_grid() {
+void EnvBlock::build_tri_grid(const Knobs& kn, hipStream_t stream) {
   envv.tg_start = nullptr;
   envv.tg_list = nullptr;
   if (!have_env || !have_robot || envv.n_tri <= 0 || envv.n_levels < 1) return;
@@ -724,29 +760,59 @@ void Ctx::grid_setup(const double limits[6], double cell) {
   gridv.ovf = g_ovf.as<sffk::GridItem>();
   gridv.lite = g_lite.as<sffk::GridItem32>();
   gridv.ovf_lite = g_ovf_lite.as<sffk::GridItem32>();
-  // the round's own grid: same cells, its own buckets / overflow list, all counters zero between rounds
+  // the round's own grid: same cells, its own buckets / overflow list, all counters zero between rounds.  Here its
+  // geometry and the counter the wave-end launches and status blocks read; the rest in round_grid()
   tgridv = gridv;
   tgridv.bk = 8;
   tgridv.ovf_cap = std::max(1 << 20, tgrid_ovf_min);   // >= the samples of one round (Forest::Forest)
+  tgridv.cnt = nullptr;
+  tgridv.items = nullptr;
+  tgridv.ovf = nullptr;
+  tgridv.lite = nullptr;
+  tgridv.ovf_lite = nullptr;
+  tgridv.occ = nullptr;
+  t_ovfcnt.ensure(16);
+  HIPCHK(hipMemsetAsync(t_ovfcnt.p, 0, 16, stream));
+  tgridv.ovf_cnt = t_ovfcnt.as<int32_t>();
+  grid_on = true;
+  grid_inserted = 0;
+  const bool had_round = round_ready;
+  round_ready = false;
+  if (!round_lazy || had_round) round_grid();   // (a member context: only once a round engine has asked for it)
+}
+void Ctx::round_grid() {
+  if (round_ready || !grid_on) return;
+  HIPCHK(hipSetDevice(device));
+  const size_t ncells = (size_t)tgridv.nx * tgridv.ny * tgridv.nz;
   t_cnt.ensure(ncells * sizeof(int32_t));
   t_items.ensure(ncells * tgridv.bk * sizeof(sffk::GridItem));
-  t_ovfcnt.ensure(16);
   t_ovf.ensure((size_t)tgridv.ovf_cap * sizeof(sffk::GridItem));
   t_lite.ensure(ncells * tgridv.bk * sizeof(sffk::GridItem32));
   t_ovf_lite.ensure((size_t)tgridv.ovf_cap * sizeof(sffk::GridItem32));
   HIPCHK(hipMemsetAsync(t_cnt.p, 0, ncells * sizeof(int32_t), stream));
-  HIPCHK(hipMemsetAsync(t_ovfcnt.p, 0, 16, stream));
   tgridv.cnt = t_cnt.as<int32_t>();
   tgridv.items = t_items.as<sffk::GridItem>();
-  tgridv.ovf_cnt = t_ovfcnt.as<int32_t>();
   tgridv.ovf = t_ovf.as<sffk::GridItem>();
   tgridv.lite = t_lite.as<sffk::GridItem32>();
   tgridv.ovf_lite = t_ovf_lite.as<sffk::GridItem32>();
   t_occ.ensure((ncells / 32 + 2) * 4);
   HIPCHK(hipMemsetAsync(t_occ.p, 0, (ncells / 32 + 2) * 4, stream));
   tgridv.occ = t_occ.as<uint32_t>();
-  grid_on = true;
-  grid_inserted = 0;
+  round_ready = true;
+}
+// device memory held by this context's own buffers, as sums of capacities (sffgpu_ctx_get_memory)
+void Ctx::memory(sffgpu_ctx_memory* out) const {
+  auto sum = [](std::initializer_list<const DevBuf*> l) { size_t s = 0; for (const DevBuf* b : l) s += b->cap; return (uint64_t)s; };
+  *out = sffgpu_ctx_memory{};
+  out->env_bytes = env_built_here ? (uint64_t)env->device_bytes() : 0;
+  out->env_holders = (uint64_t)env.use_count();
+  out->store_bytes = sum({&sx, &sy, &sz, &syaw, &spitch, &sroll, &stree, &spos});
+  out->grid_bytes = sum({&g_cnt, &g_items, &g_ovfcnt, &g_ovf, &g_lite, &g_ovf_lite, &t_ovfcnt});
+  out->round_grid_bytes = sum({&t_cnt, &t_items, &t_ovf, &t_occ, &t_lite, &t_ovf_lite});
+  out->other_bytes = sum({&d_a, &d_b, &d_c, &d_d, &d_e, &d_f, &d_g, &d_h, &sm_dev, &r_in, &r_out, &r_q, &r_cnt, &r_hidx, &r_hdist, &r_sega, &r_segb,
+                          &r_items, &r_items2, &r_sub, &r_center, &r_qrec, &r_out2, &rr_q1, &rr_q2, &rr_a, &rr_out, &rr_sq, &rr_np, &rr_alt, &rr_q2b, &rr_sqb});
+  for (const SegJob& J : seg_job) out->other_bytes += sum({&J.ids, &J.a, &J.b, &J.c});
+  out->total_bytes = out->env_bytes + out->store_bytes + out->grid_bytes + out->round_grid_bytes + out->other_bytes;
 }
 void Ctx::grid_insert_new() {
   if (!grid_on || grid_inserted >= store_n) return;
@@ -813,12 +879,12 @@ void Ctx::grid_grow_list() {
 
 // slack that makes the fp32 sweep filter a superset of the exact fp64 test: a few fp32 ulps of
 // the largest coordinate magnitude in play
-double Ctx::sweep_eps() const { return std::max(store_maxabs, env_maxabs) * std::ldexp(1.0, -20); }
+double Ctx::sweep_eps() const { return std::max(store_maxabs, env_maxabs()) * std::ldexp(1.0, -20); }
 
 // ------------------------------------------------------------------ batched primitives
 void Ctx::collide_poses(const double* pos6, int n, uint8_t* hit, bool explicit_rt) {
   if (n <= 0) return;
-  if (!have_env || !have_robot) throw HipError{"collide_poses: upload ENV and ROBOT meshes first"};
+  if (!have_env() || !have_robot()) throw HipError{"collide_poses: upload ENV and ROBOT meshes first"};
   HIPCHK(hipSetDevice(device));
   const size_t per = (explicit_rt ? 12 : 6) * sizeof(double);
   h_a.ensure((size_t)n * per);
@@ -850,7 +916,7 @@ void Ctx::collide_segments_refs(const int32_t* ida, const int32_t* idb, int n, u
 void Ctx::collide_segments_core(const double* a6, const double* b6, const int32_t* ida, const int32_t* idb, int n,
                                 uint8_t* is_free, int32_t* first_hit, int32_t* n_samples, const double* extra_dev) {
   if (n <= 0) return;
-  if (!have_env || !have_robot) throw HipError{"collide_segments: upload ENV and ROBOT meshes first"};
+  if (!have_env() || !have_robot()) throw HipError{"collide_segments: upload ENV and ROBOT meshes first"};
   HIPCHK(hipSetDevice(device));
   // sample counts (src/problemStruct.h:155-156) and result presets are computed on the device, then the slot
   // table is compacted into (edge, chunk) work items for the persistent edge kernel
@@ -963,7 +1029,7 @@ void Ctx::seg_refs_begin(int which, const int32_t* ida, const int32_t* idb, int 
   J.n = n;
   if (n <= 0) return;
   if (!rr_np_dev) throw HipError{"seg_refs_begin: no rrt_chain has run"};
-  if (!have_env || !have_robot) throw HipError{"collide_segments: upload ENV and ROBOT meshes first"};
+  if (!have_env() || !have_robot()) throw HipError{"collide_segments: upload ENV and ROBOT meshes first"};
   HIPCHK(hipSetDevice(device));
   if (!J.ev) HIPCHK(hipEventCreateWithFlags(&J.ev, hipEventDisableTiming));
   const size_t pb = (size_t)n * 6 * sizeof(double);
@@ -1103,7 +1169,7 @@ void Ctx::rrt_chain(const double* rnd6, const int32_t* tree, int n, double dist,
                     int32_t* near_idx, double* near_d, int32_t* near_cnt, int32_t* mate, RrtRows& R, double conn_r, int conn_cap,
                     int alt_cap, int32_t* alt_slot, int32_t* alt_mate, int32_t* n_alt, RrtRows* R2) {
   if (n <= 0) return;
-  if (!have_env || !have_robot) throw HipError{"rrt_chain: upload ENV and ROBOT meshes first"};
+  if (!have_env() || !have_robot()) throw HipError{"rrt_chain: upload ENV and ROBOT meshes first"};
   HIPCHK(hipSetDevice(device));
   const int K1 = 2;
   if (alt_cap > n) alt_cap = n;

@@ -8,6 +8,7 @@
 #include <algorithm>
 #include <functional>
 #include <map>
+#include <memory>
 #include <unordered_set>
 #include <string>
 #include <utility>
@@ -102,6 +103,33 @@ struct HitRec {
 // of a sharded forest repeats; T_EXCHANGE: pack + all-gather + unpack of the answer records
 enum TimerKind { T_SWEEP = 0, T_COLLIDE = 1, T_SAMPLE = 2, T_COMMIT = 3, T_EXCHANGE = 4, T_KINDS = 5 };
 
+// The collision models of a context: everything sffgpu_mesh_upload builds.  Written by upload() and the three build_*
+// functions only - each ends with every copy and launch it enqueued waited for -, read by every kernel through the two
+// views.  A context holds its block through a shared_ptr; the contexts made by sffgpu_create_member hold their owner's, so
+// a block with more than one holder is never written again (Ctx::upload_mesh refuses) and goes with its last holder.
+struct EnvBlock {
+  int device = 0;
+  DevBuf env_tri, env_box, env_plane, level_box[SFFK_MAX_LEVELS], rob_tri, env_clear, env_clear_edge, env_ext, env_cand;
+  DevBuf env_tg_start, env_tg_list;
+  std::vector<double> h_plane, h_rob;   // host copies (robot extents along the triangle normals)
+  sffk::EnvView envv{};
+  sffk::RobotView robv{};
+  bool have_env = false, have_robot = false;
+  double env_maxabs = 1.0;
+  double env_lo[3] = {0, 0, 0}, env_hi[3] = {0, 0, 0};
+  long long clear_cells = 0;   // cells of the clearance grid (0 = none)
+  // kn: the uploading context's snapshot (the knobs that shape the models); stream: its launch stream, idle on return
+  void upload(const Knobs& kn, hipStream_t stream, int role, const double* tri9, int n);
+  void build_robot_extents(const Knobs& kn);
+  void build_clearance(const Knobs& kn, hipStream_t stream);
+  void build_tri_grid(const Knobs& kn, hipStream_t stream);   // cell -> triangle lists for the collision kernels' broad phase
+  size_t device_bytes() const;
+  explicit EnvBlock(int dev) : device(dev) {}
+  EnvBlock(const EnvBlock&) = delete;
+  EnvBlock& operator=(const EnvBlock&) = delete;
+  ~EnvBlock();
+};
+
 struct Ctx {
   int device = 0;
   Knobs kn;                                   // the environment as it was at the last creation entry (knobs.h says which)
@@ -113,10 +141,14 @@ struct Ctx {
   hipEvent_t ev_mid = nullptr, ev_early = nullptr;
   std::string err;
 
-  // collision models
-  DevBuf env_tri, env_box, env_plane, level_box[SFFK_MAX_LEVELS], rob_tri, env_clear, env_clear_edge, env_ext, env_cand;
-  std::vector<double> h_plane, h_rob;   // host copies (robot extents along the triangle normals)
-  void build_robot_extents();
+  // collision models: the block (its own, or - a member context - its owner's) and this context's copies of the two views
+  std::shared_ptr<EnvBlock> env;
+  bool env_built_here = true;   // false: a context made by sffgpu_create_member (the block's bytes are not its own)
+  sffk::EnvView envv{};
+  sffk::RobotView robv{};
+  bool have_env() const { return env->have_env; }
+  bool have_robot() const { return env->have_robot; }
+  double env_maxabs() const { return env->env_maxabs; }
   // RCCL communicator of the library's own (multi-GPU device engine; librccl is bound at run time)
   void* rccl_comm = nullptr;
   int rccl_rank = 0, rccl_world = 1;
@@ -130,15 +162,6 @@ struct Ctx {
     return (xchg_fn && xchg_world == world && xchg_rank == rank) || (rccl_comm && rccl_world == world && rccl_rank == rank);
   }
   static void rccl_unique_id(uint8_t* id128);
-  sffk::EnvView envv{};
-  sffk::RobotView robv{};
-  bool have_env = false, have_robot = false;
-  double env_maxabs = 1.0;
-  double env_lo[3] = {0, 0, 0}, env_hi[3] = {0, 0, 0};
-  long long clear_cells = 0;   // cells of the clearance grid (0 = none)
-  void build_clearance();
-  void build_tri_grid();       // cell -> triangle lists for the collision kernels' broad phase
-  DevBuf env_tg_start, env_tg_list;
 
   // node store
   int store_cap = 0, store_n = 0;
@@ -151,6 +174,13 @@ struct Ctx {
   DevBuf g_cnt, g_items, g_ovfcnt, g_ovf, g_lite, g_ovf_lite;
   DevBuf t_cnt, t_items, t_ovfcnt, t_ovf, t_occ, t_lite, t_ovf_lite;   // the round's own grid (same cells; filled and emptied every round)
   sffk::GridView tgridv{};
+  // A member context (sffgpu_create_member) carries of the round grid only the counter t_ovfcnt - tgridv has its geometry
+  // and null item pointers - until a round engine needs the rest: the one-wavefront loops never read it.  round_grid()
+  // allocates and zeroes it as grid_setup does for every other context; called on the host before anything that reads
+  // tgridv is enqueued or captured (never inside a capture).  A re-celling keeps the state: lean stays lean.
+  bool round_lazy = false;    // a member context
+  bool round_ready = false;   // the round grid's buffers stand behind tgridv
+  void round_grid();
   int grid_inserted = 0;
   void grid_setup(const double limits[6], double cell);
   void grid_insert_new();   // store entries [grid_inserted, store_n)
@@ -197,8 +227,9 @@ struct Ctx {
   bool timing_on = true, timed_now = true;
   double kernel_ms_total(int kind) const;
 
-  explicit Ctx(int dev);
+  explicit Ctx(int dev, const Ctx* owner = nullptr);   // owner: the new context holds owner's models (sffgpu_create_member)
   ~Ctx();
+  void memory(sffgpu_ctx_memory* out) const;
   void sync();  // stream sync + harvest timers
   hipEvent_t get_event();
   void time_begin(int kind);

@@ -101,7 +101,7 @@ Forest::Forest(Ctx* c, const sffgpu_forest_cfg& cf, const double* roots6, int n_
   if (cfg.world < 1) cfg.world = 1;
   if (cfg.rank < 0 || cfg.rank >= cfg.world) throw HipError{"forest: rank outside [0, world)"};
   if (n_roots < 1) throw HipError{"forest: at least one root"};
-  if (!c->have_env || !c->have_robot) throw HipError{"forest: upload ENV and ROBOT meshes first"};
+  if (!c->have_env() || !c->have_robot()) throw HipError{"forest: upload ENV and ROBOT meshes first"};
   rng.reseed(cfg.seed);
   if (cfg.wave >= 64) rng_ahead.assign((size_t)8 * cfg.wave + 4096, 0);
   num_roots = n_roots + (cfg.has_goal ? 1 : 0);
@@ -455,6 +455,7 @@ void Forest::round_begin() {
   HIPCHK(hipSetDevice(c.device));
   if (pending_round) throw HipError{"forest: round_begin called twice without round_commit"};
   if (dev.active) dev_to_host();   // the round protocol runs on the host path
+  c.round_grid();                  // (a member context has none until here: the samples of a round go through it)
   if (!in_wave) {
     if (terminated()) return;
     begin_wave();

@@ -1164,6 +1164,7 @@ void Forest::dev_enqueue_wave_kernels(bool sharded, size_t words) {
 void Forest::dev_enqueue_wave(int slot) {
   Ctx& c = *ctx;
   DevEngine& d = dev;
+  c.round_grid();           // (a member context: the round grid comes with the first wave of rounds - here, ahead of the capture below)
   d.wr.wait_on(c.stream);   // the words this wave may read have to be resident
   // (SFFGPU_TEST_EXCHANGE_SELF: a one-rank forest packs, all-gathers and unpacks too - the collective on one GPU)
   const bool self_exchange = kn.test_exchange_self;
@@ -1313,6 +1314,7 @@ bool Forest::dev_wave_begin() {
   if (!dev.on) throw HipError{"forest: the device engine does not drive this forest"};
   HIPCHK(hipSetDevice(ctx->device));
   exchange_timer_drop();
+  ctx->round_grid();   // (a member context: before the caller's first dev_round_eval)
   if (!dev.active) dev_upload_state();
   const sffk::DevCtrl& k = dev.last;
   if (!k.in_wave && k.terminated) return false;

@@ -25,7 +25,7 @@ Rrt::Rrt(Ctx* c, const sffgpu_rrt_cfg& cf, const double* roots6, int n_roots) : 
   if (cfg.dim != 2 && cfg.dim != 6) throw HipError{"rrt: dim must be 2 or 6"};
   if (n_roots < 1) throw HipError{"rrt: at least one root"};
   if (cfg.priority_bias != 0 && !cfg.has_goal) throw HipError{"rrt: goal bias needs a goal (src/main.cpp:330-331)"};
-  if (!c->have_env || !c->have_robot) throw HipError{"rrt: upload ENV and ROBOT meshes first"};
+  if (!c->have_env() || !c->have_robot()) throw HipError{"rrt: upload ENV and ROBOT meshes first"};
   if (cfg.lazy_edge && (n_roots != 1 || cfg.has_goal || cfg.priority_bias != 0))
     throw HipError{"rrt: lazy_edge grows ONE tree from one root towards cfg.goal (has_goal = 0, no goal bias)"};
   rng.reseed(cfg.seed);

@@ -185,7 +185,7 @@ sffk::RrtSeqArgs Rrt::batch_prepare(int iters) {
   a.dist_tree = cfg.dist_tree;
   a.sampling_dist = cfg.sampling_dist;
   // (the store's largest coordinate is only known up to the host mirror: the nodes the kernel adds lie within one step of the limits)
-  double reach = std::max(c.store_maxabs, c.env_maxabs);
+  double reach = std::max(c.store_maxabs, c.env_maxabs());
   for (int k = 0; k < 6; ++k) reach = std::max(reach, std::fabs(cfg.limits[k]) + cfg.sampling_dist);
   a.sweep_abs_eps = reach * std::ldexp(1.0, -20);
   a.cell_edge = c.grid_cell;

@@ -45,7 +45,7 @@ void run_smooth_batch(SmoothMember* members, int n, int* failed) {
         const int len = (int)m.plans[p]->size();
         if (len == 2) steps[(size_t)i][p].push_back(0);   // (g = 1: no candidate, t = g - 1)
         if (len < 3) continue;
-        if (!m.ctx->have_env || !m.ctx->have_robot) throw HipError{"smooth_paths: upload ENV and ROBOT meshes first"};
+        if (!m.ctx->have_env() || !m.ctx->have_robot()) throw HipError{"smooth_paths: upload ENV and ROBOT meshes first"};
         tab.push_back(PathRef{i, (int)p, len, total});
         total += (size_t)len;
         lds = std::max(lds, sffk::collide_lds_bytes(m.ctx->robv.n_tri, 1));
