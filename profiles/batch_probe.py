@@ -5,7 +5,8 @@ Legs (every repeat of every leg is a child process of its own, legs alternated i
   a  S.run_batch of the B forests (B contexts)                                         - this build (--a-builds new,parent:
                                                                                           and the parent's, alternated)
   b  the B forests one after another through Forest.run (k_spec_waves)                 - the PARENT commit's build
-  c  as b with SFFGPU_SPEC=0 (the single-forest k_seq_waves entry, whose body moved)    - the parent's build AND this one
+                                                                                          (--b-builds new,parent: and this one)
+  c  as b with SFFGPU_SPEC=0 (the single wavefront: a batch of one on this build)       - the parent's build AND this one
 
 The parent's build is a libsffgpu.so made from `git archive <parent>` in a directory outside git; --parent-lib names it
 (it is loaded through SFFGPU_LIB; its statistics struct is 8 bytes shorter, batch_launches reads 0 there).
@@ -135,6 +136,7 @@ def main():
     ap.add_argument("--c-size", type=int, default=8)  # leg c
     ap.add_argument("--legs", default="a,b,c")
     ap.add_argument("--a-builds", default="new")      # leg a; "new,parent": the parent's run_batch too (a parent that has one)
+    ap.add_argument("--b-builds", default="parent")   # leg b; "new,parent": this build's Forest.run too, alternated
     ap.add_argument("--share-env", action="store_true")   # leg a, this build: contexts 1.. are members of context 0
     ap.add_argument("--child-timeout", type=int, default=420)
     ap.add_argument("--out", default=OUT)
@@ -148,7 +150,8 @@ def main():
         opt = 1 if kind == "star" else 0
         sizes_a = [int(x) for x in a.batch_sizes.split(",")] if a.batch_sizes else ([1, 32, 64] if opt else [1, 8, 32, 64, 128])
         sizes_b = [int(x) for x in a.seq_sizes.split(",")] if a.seq_sizes else ([1, 64] if opt else [1, 8, 64])
-        legs = [("a", build, B) for B in sizes_a for build in a.a_builds.split(",")] + [("b", "parent", B) for B in sizes_b]
+        legs = [("a", build, B) for B in sizes_a for build in a.a_builds.split(",")] + \
+               [("b", build, B) for B in sizes_b for build in a.b_builds.split(",")]
         if a.c_size > 0:
             legs += [("c", "parent", a.c_size), ("c", "new", a.c_size)]
         legs = [l for l in legs if l[0] in a.legs.split(",")]

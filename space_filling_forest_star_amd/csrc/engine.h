@@ -207,7 +207,7 @@ struct Ctx {
   DevBuf sm_dev;   // path smoothing on the device (smooth_batch.cpp): path table | control blocks | output rows | positions,
   PinBuf sm_pin;   // of the call whose first member this context belongs to, and their pinned image
   // round pipeline buffers of the forest engine (kept apart from the batch entry points' scratch)
-  DevBuf r_in, r_out, r_q, r_cnt, r_hidx, r_hdist, r_sega, r_segb, r_items, r_items2, r_sub, r_center;
+  DevBuf r_in, r_out, r_q, r_cnt, r_sega, r_segb, r_items, r_items2, r_sub, r_center;
   DevBuf r_qrec;   // per sample: QRec (kernels.h), written by the sampling kernels for k_query_block
   DevBuf r_out2;   // device engine: positions + parent distances of the odd rounds of a wave (see Forest::dev_enqueue_wave_kernels)
   PinBuf p_in, p_out;
@@ -398,13 +398,15 @@ struct DevEngine {
   sffk::DevCtrl last{};         // status block after the last completed wave
   uint32_t status_next = 0;     // sequence number the next published block will carry
   uint32_t status_of[2] = {0, 0};   // ... and the ones the two enqueued waves' blocks carry
-  bool status_copied[2] = {true, true};   // the slot's block came by a copy into h_ctrl[slot] (k_seq_waves, SFFGPU_NO_ZC_STATUS) instead of
+  bool status_copied[2] = {true, true};   // the slot's block came by a copy into h_ctrl[slot] (k_seq_waves_batch, SFFGPU_NO_ZC_STATUS) instead of
                                           // being written into the pinned ring by the wave's last kernel (sffk::status_publish)
   // waves of one slot, speculated (k_spec_waves): scenario tree, control blocks, records (sffk::SpecArgs)
   DevBuf spec_tab, spec_area;
   DevBuf qclk_sh;               // the query kernel's clock bracket, 64 shards (sffk::DevForestView::qclk_sh)
   int spec_n_sc = 0, spec_sets = 0, spec_tm = 0;
   bool spec_off = false;        // SFFGPU_SPEC=0, or a launch stalled (its workgroups were not resident together)
+  PinBuf h_seq;                 // the single-wavefront loop's arguments (sffk::SeqArgs) for one forest: the pinned slot they are
+  DevBuf seq_args;              // built in and the device slot the kernel reads them from (run_device_seq)
   uint64_t seq_pick_slack = 0;  // priority frontier in the loop of waves of one slot: extra engine words for the next launch (a pick's
                                 // redraws are not bounded; the launch before ran no wave for want of words - Forest::seq_note_launch)
 };
@@ -441,8 +443,12 @@ struct Forest {
   size_t dev_exchange_bytes() const;
   void run_device(int max_waves);
   bool batch_eligible() const;      // waves of one slot the single-wavefront loop can run: may be a member of run_forest_batch
-  bool seq_eligible() const;        // ... and sffgpu_forest_run takes that loop (k_seq_waves / k_spec_waves) for them
+  bool seq_eligible() const;        // ... and sffgpu_forest_run takes that loop (k_seq_waves_batch / k_spec_waves) for them
   void run_device_seq(int max_waves);
+  // the loop's template instance for this forest: bit 0 SFF*, bit 1 priority frontier, bit 2 goal.  The arguments say the
+  // same (dev_view: f.goal_id >= 0 exactly with cfg.has_goal; f.prio.n_heaps > 0 exactly with use_priority(), since
+  // device_eligible() admits a priority forest only with a heap or more and dev_upload_state uploads them before a launch)
+  int seq_kind() const { return (cfg.optimize ? 1 : 0) | (use_priority() ? 2 : 0) | (cfg.has_goal ? 4 : 0); }
   // one launch of that loop in two halves (run_device_seq, and run_forest_batch below, which launches many forests at once)
   int seq_launch_waves(int waves_left) const;     // waves the next launch may run (waves_left: the caller's bound, 0 = none)
   uint64_t seq_words_end(int batch) const;         // ... and the ring position its engine words have to reach
@@ -450,7 +456,7 @@ struct Forest {
   void seq_note_launch(uint64_t waves_before);     // after dev_finish_wave: did the launch get anywhere (priority mode's word slack)
   sffk::SeqArgs seq_prepare(int batch);            // tops the ring up to there, builds the kernel's arguments
   void seq_lists_fault();                          // SFFK_FAULT_LISTS came back: that wave on the host-replay engine, state back up
-  bool spec_setup();                // the speculative kernel's scenario tree and buffers; false = k_seq_waves runs the loop
+  bool spec_setup();                // the speculative kernel's scenario tree and buffers; false = k_seq_waves_batch runs the loop
   bool seq_suspended = false;
   void sync_host();             // refresh the host mirror (nodes, frontier, borders, counters) from the device
   void fill_stats(sffgpu_forest_stats* out);

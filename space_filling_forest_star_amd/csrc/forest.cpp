@@ -314,7 +314,7 @@ Forest::~Forest() {
                     &dev.s_evd, &dev.s_acc, &dev.s_backup, &dev.s_items, &dev.s_dbg, &dev.s_hist, &dev.w_acc, &dev.acc_pref, &dev.ustate32, &dev.wg_pub, &dev.commit_seq, &dev.kc_trace, &x_send, &x_recv,
                     &dev.hp_base, &dev.hp_size, &dev.hp_v, &dev.hp_key, &dev.hp_pos, &dev.hp_ref, &dev.hp_gen, &dev.hp_cnt, &dev.slot_tree, &dev.slot_heap, &dev.slot_idx, &dev.slot_word, &dev.hp_plan,
                     &dev.ord_hist, &dev.ord_start, &dev.ord_key, &dev.ord_rank, &dev.ord_pos, &dev.ord_lst, &dev.ord_cnt,
-                    &dev.w_ev, &dev.ev_h, &dev.ev_nb, &dev.ev_raw, &dev.spec_tab, &dev.spec_area, &dev.qclk_sh};
+                    &dev.w_ev, &dev.ev_h, &dev.ev_nb, &dev.ev_raw, &dev.spec_tab, &dev.spec_area, &dev.qclk_sh, &dev.seq_args};
   if (dev.inited) {
     (void)hipSetDevice(ctx->device);
     (void)hipStreamSynchronize(ctx->stream);
@@ -322,6 +322,7 @@ Forest::~Forest() {
   }
   for (DevBuf* b : bufs) b->release();
   dev.h_ctrl.release();
+  dev.h_seq.release();
   dev.wr.release();
   dev.h_trig.release();
   if (dev.wave_graph) (void)hipGraphExecDestroy(dev.wave_graph);
@@ -495,8 +496,9 @@ void Forest::round_begin() {
   auto _t1 = Clock::now();
   // ---- one GPU pipeline per round, a single host sync at its end:
   //   H2D {engine words, expanded ids, ForceChildren flags}
-  //   k_sample_steer -> k_store_write (temporaries) -> k_sweep -> k_classify -> k_collide_poses
-  //   -> k_collide_segments_dyn -> D2H {samples, flags, neighbour records, pose / edge answers}
+  //   k_sample_steer (sample, the round's temporaries) -> k_query_classify / k_query_block (neighbour query,
+  //   classification, clearance cull) -> k_collide_items (exact poses and edges) -> k_settle
+  //   -> D2H {samples, flags, neighbour records, pose / edge answers}
   const int words_per = cfg.dim == 2 ? 1 : 6;
   const int CAP = kn.test_hitcap, NBCAP = kn.test_nbcap, STRIDE = 1 + NBCAP;
   // packed host input: words (n*6 u64) | parent (n i32) | force (n u8)
@@ -527,7 +529,7 @@ void Forest::round_begin() {
   const uint64_t* d_words = reinterpret_cast<const uint64_t*>(c.r_in.as<char>() + in_words);
   const int32_t* d_parent = reinterpret_cast<const int32_t*>(c.r_in.as<char>() + in_parent);
   const uint8_t* d_force = reinterpret_cast<const uint8_t*>(c.r_in.as<char>() + in_force);
-  // device output block in two D2H copies.  Early part (complete after k_classify, copied on a second stream
+  // device output block in two D2H copies.  Early part (complete after the query kernel, copied on a second stream
   // while the collision kernels run): pos | pdist | in_lim | records | edge sample counts.  Late part: edge
   // first hits (0 = redo on the host path) | ctrl (32 ints incl. the u64 settle counters) | pose answers | settle codes.
   // records: flags (n) | nnb (n) | nb ids (n*NBCAP) | nb meta (n*NBCAP)
@@ -548,8 +550,6 @@ void Forest::round_begin() {
   uint8_t* d_pose = reinterpret_cast<uint8_t*>(dout + o_pose);
   c.r_q.ensure((size_t)n * sizeof(sffk::SweepQuery));
   c.r_cnt.ensure((size_t)n * 4);
-  c.r_hidx.ensure((size_t)n * CAP * 4);
-  c.r_hdist.ensure((size_t)n * CAP * 8);
   c.r_sega.ensure((size_t)n * STRIDE * 48);
   c.r_segb.ensure((size_t)n * STRIDE * 48);
   HIPCHK(hipMemcpyAsync(c.r_in.p, c.p_in.p, in_bytes, hipMemcpyHostToDevice, c.stream));
@@ -597,8 +597,8 @@ void Forest::round_begin() {
   ca.parent = d_parent;
   ca.force = d_force;
   ca.cnt = c.r_cnt.as<int32_t>();
-  ca.hit_idx = c.r_hidx.as<int32_t>();
-  ca.hit_dist = c.r_hdist.as<double>();
+  ca.hit_idx = nullptr;
+  ca.hit_dist = nullptr;
   ca.tree = c.stree.as<int32_t>();
   ca.pos = c.spos.as<double>();
   ca.rec_flags = d_rec;

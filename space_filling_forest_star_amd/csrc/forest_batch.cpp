@@ -1,7 +1,7 @@
 // forest_batch.cpp — forest batches: many independent forests of waves of ONE slot advanced in lock step.
 //
 // Waves of one slot are the reference's own loop order (src/forest.h:122-202), and one forest of them keeps one wavefront
-// busy (k_seq_waves) - or, speculated, a couple of hundred workgroups for a factor of four (k_spec_waves).  Independent
+// busy (k_seq_waves_batch) - or, speculated, a couple of hundred workgroups for a factor of four (k_spec_waves).  Independent
 // forests need neither speculation nor co-residency: k_seq_waves_batch gives every member a wavefront of its own, and the
 // host does for every member what run_device_seq does for one.  The lock step itself is run_lockstep (batch_lockstep.h);
 // here is what is a forest's own in it:
@@ -18,8 +18,7 @@ namespace sff {
 namespace {
 struct ForestFamily {
   using Args = sffk::SeqArgs;
-  // the template instance that runs a member: bit 0 SFF*, bit 1 priority frontier, bit 2 goal
-  static constexpr int n_kinds = 8;
+  static constexpr int n_kinds = 8;   // the template instance that runs a member: Forest::seq_kind
   Forest* const* m;
   int n, max_waves;
   std::vector<uint64_t> w0, w_launch;
@@ -58,7 +57,7 @@ struct ForestFamily {
     w_launch[i] = m[i]->dev.last.waves;
     return m[i]->seq_prepare(waves);
   }
-  int kind(int i) { return (m[i]->cfg.optimize ? 1 : 0) | (m[i]->use_priority() ? 2 : 0) | (m[i]->cfg.has_goal ? 4 : 0); }
+  int kind(int i) { return m[i]->seq_kind(); }
   hipStream_t stream(int i) { return m[i]->ctx->stream; }
   StatusBlock status(int i) { return {m[i]->dev.h_ctrl.p, m[i]->dev.ctrl.p, sizeof(sffk::DevCtrl)}; }
   hipError_t launch(hipStream_t s, const Args* a, int count, int kind, size_t lds) {

@@ -40,7 +40,7 @@ bool Forest::device_eligible() const {
   // except in waves of ONE slot under SFFGPU_PRIO_GOAL_LOOP=1 (below)
   if (!use_priority()) return true;
   if (cfg.has_goal) {
-    // priority + goal: the single-wavefront loop only (k_seq_waves<., true, true>), so waves of one slot, one rank, a lane
+    // priority + goal: the single-wavefront loop only (k_seq_waves_batch<., true, true>), so waves of one slot, one rank, a lane
     // per tree, and only for a forest created under SFFGPU_PRIO_GOAL_LOOP=1 - neither SFFGPU_PRIO_LOOP nor SFFGPU_GOAL_LOOP
     // covers the combination.  One heap per start tree (src/forest.h:104-108), none for the goal's tree.
     if (!kn.prio_goal_loop || !kn.prio_device || kn.no_seq || num_roots > 64 || cfg.wave != 1 || cfg.world > 1) return false;
@@ -50,7 +50,7 @@ bool Forest::device_eligible() const {
   }
   // (measured on dense_3D, 100 k nodes: 73 k nodes/s at waves of 64 slots against the host engine's 29 k, 0.83 M at 1 024
   // against 98 k, 1.6 M at 8 192; waves of one slot - the reference's own loop - stay on the host engine unless the forest
-  // was created under SFFGPU_PRIO_LOOP=1, which gives them to the single-wavefront loop (k_seq_waves<., true>);
+  // was created under SFFGPU_PRIO_LOOP=1, which gives them to the single-wavefront loop (k_seq_waves_batch<., true>);
   // SFFGPU_PRIO_DEVICE=0 keeps the whole mode there)
   const int min_wave = !kn.prio_device ? 0x7fffffff : (kn.prio_loop && !kn.no_seq && num_roots <= 64) ? 1 : 2;
   if (cfg.wave < min_wave || cfg.world > 1) return false;
@@ -474,7 +474,7 @@ void Forest::dev_upload_state() {
     // (room for four waves' worth - and for everything the host engine may have generated ahead when the state moves
     // to the device in the middle of a run)
     uint64_t ring_words = next_pow2(std::max<uint64_t>(4 * d.max_wave_words, (uint64_t)rng_ahead.size() + 2 * d.max_wave_words + 64));
-    if (cfg.wave == 1) ring_words = std::max<uint64_t>(ring_words, 1 << 18);   // (k_seq_waves: thousands of waves per launch)
+    if (cfg.wave == 1) ring_words = std::max<uint64_t>(ring_words, 1 << 18);   // (k_seq_waves_batch: thousands of waves per launch)
     d.wr.init(ring_words);
     if (cfg.libm_sampling) {
       d.trig.ensure((size_t)d.wr.ring_words * 24);
@@ -1339,7 +1339,7 @@ bool Forest::seq_eligible() const { return batch_eligible() && !kn.no_seq && !se
 // 0 .. TM-1 | all fail) to SFFGPU_SPEC_DEPTH waves (default 3: 1 + 6 + 36 scenarios at ThresholdMisses = 5, one workgroup
 // per scenario and attempt), cut where the grid would no longer be resident at once; SFF*: the chain of all-fail
 // scenarios.  SFFGPU_SPEC_SETS sets of workers take the steps in turn (default 1).  SFFGPU_SPEC=0 keeps the single
-// wavefront (k_seq_waves).  All in the forest's snapshot (Forest::kn).
+// wavefront (k_seq_waves_batch).  All in the forest's snapshot (Forest::kn).
 static const size_t SPEC_HEAD = 4096;   // bytes in front of the records: 4 x 64 control-block granules, the step word
 bool Forest::spec_setup() {
   DevEngine& d = dev;
@@ -1385,7 +1385,7 @@ bool Forest::spec_setup() {
   return true;
 }
 
-// waves of ONE slot (the reference's own order): k_seq_waves runs whole outer iterations back to back inside one launch,
+// waves of ONE slot (the reference's own order): k_seq_waves_batch runs whole outer iterations back to back inside one launch,
 // thousands of waves per launch; the host tops the engine-word ring up between launches and handles what the round engine's
 // host side handles (growth, re-celling, a list overflow -> that wave is finished on the host-replay engine)
 // ---- the two halves of one launch of the single-wavefront loop, shared by run_device_seq (one forest) and run_forest_batch
@@ -1521,7 +1521,16 @@ void Forest::run_device_seq(int max_waves) {
       HIPCHK(hipMemsetAsync(d.spec_area.p, 0, d.spec_area.cap, c.stream));
       sffk::launch_spec_waves(c.stream, sa);
     } else {
-      HIPCHK(sffk::launch_seq_waves(c.stream, a));
+      // the loop's one entry, with this forest as its only member: the arguments go up from the pinned slot ahead of the
+      // launch.  (The slot is free to write: dev_finish_wave below waits for the launch - and so for this copy - before
+      // the loop comes round.)
+      d.h_seq.ensure(sizeof a);
+      d.seq_args.ensure(sizeof a);
+      *d.h_seq.as<sffk::SeqArgs>() = a;
+      HIPCHK(hipMemcpyAsync(d.seq_args.p, d.h_seq.p, sizeof a, hipMemcpyHostToDevice, c.stream));
+      const int kind = seq_kind();
+      HIPCHK(sffk::launch_seq_waves_batch(c.stream, d.seq_args.as<sffk::SeqArgs>(), 1, (kind & 1) != 0, (kind & 2) != 0, (kind & 4) != 0,
+                                          sffk::collide_lds_bytes(a.rob.n_tri, 1)));
     }
     HIPCHK(hipMemcpyAsync(d.h_ctrl.as<sffk::DevCtrl>(), d.ctrl.p, sizeof(sffk::DevCtrl), hipMemcpyDeviceToHost, c.stream));
     d.status_copied[0] = true;
@@ -1551,7 +1560,7 @@ void Forest::run_device_seq(int max_waves) {
     if (spec && d.last.spec_stalled) {   // (its workgroups were not resident together: the single wavefront from here on)
       d.spec_off = true;
       if (kn.profile) {
-        fprintf(stderr, "[sffgpu k_spec_waves] a record did not arrive: back to k_seq_waves\n");
+        fprintf(stderr, "[sffgpu k_spec_waves] a record did not arrive: back to the single wavefront (k_seq_waves_batch)\n");
         const int nw = d.spec_sets * d.spec_n_sc * d.spec_tm;
         std::vector<unsigned long long> hb((size_t)nw + 8 + 34);
         HIPCHK(hipMemcpy(hb.data(), d.spec_area.as<uint8_t>() + SPEC_HEAD + (size_t)nw * SFFK_SPEC_REC * 8, hb.size() * 8, hipMemcpyDeviceToHost));

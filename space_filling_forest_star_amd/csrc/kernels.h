@@ -203,7 +203,7 @@ struct DevCtrl {
   // that begin a fresh wave, cleared when a wave is resumed - k_sample_steer then asks for slot_node[thread] at once
   int32_t act_identity;
   // waves of one slot, speculated (k_spec_waves): steps (publish -> evaluate -> commit), attempts the workers evaluated,
-  // attempts that were committed; stalled = a worker's record did not arrive in time (the host goes back to k_seq_waves)
+  // attempts that were committed; stalled = a worker's record did not arrive in time (the host goes back to k_seq_waves_batch)
   unsigned long long spec_steps, spec_evaluated, spec_committed;
   int32_t spec_stalled, spec_pad;
 };
@@ -256,7 +256,7 @@ struct DevRound {
                                // acos(1 - 2 u) of the word as u in [0, 1)} evaluated by the HOST's C library; null = the
                                // kernel's own portable trig
   int32_t words_per;           // words per sample: 6 (3-D) / 1 (2-D)
-  int32_t* parent_out;         // n: expanded node of every sample (read by k_classify)
+  int32_t* parent_out;         // n: expanded node of every sample (ClassifyArgs::parent of the round's query kernel)
   uint8_t* force_out;          // n: its ForceChildren flag
   unsigned long long* qclk;    // DevCtrl::q_t0 / q_t1, reset here for the query kernel that follows
   unsigned long long* qclk_sh; // ... and the 64 shards EVERY workgroup of that kernel reports into (DevForestView::qclk_sh)
@@ -298,14 +298,8 @@ void launch_store_write(hipStream_t s, const NodeStoreMut& st, const double* pos
 // linear sweep over store entries [first, first + n_nodes) (first must be a multiple of 4)
 void launch_sweep(hipStream_t s, const NodeStoreView& st, int first, int n_nodes, const SweepQuery* queries,
                   const double* qpos, int nq, int32_t* cnt, int32_t* hit_idx, double* hit_dist, int cap);
-// grid: insert store entries [first, first+n) / answer the queries from the cells their ball touches
+// grid: insert store entries [first, first+n)
 void launch_grid_insert(hipStream_t s, const GridView& g, const NodeStoreView& st, int first, int n);
-// tg (optional): a second grid with the same cells that holds the round's own samples (filled by k_sample_steer,
-// emptied again by k_seg_compact); query i sees its entries with id < max_id like any other
-// dev_n (optional, device memory): {number of queries, halt flag} read by the kernel instead of nq
-void launch_grid_query(hipStream_t s, const GridView& g, const GridView* tg, const NodeStoreView& st,
-                       const SweepQuery* queries, const double* qpos, int nq, int32_t* cnt, int32_t* hit_idx,
-                       double* hit_dist, int cap, const int32_t* dev_n = nullptr);
 void launch_set_tree(hipStream_t s, int32_t* tree_col, const int32_t* ids, int n, int32_t value);
 
 // ---- exact k nearest (replaces flann::Index::knnSearch: src/forest.h:317, src/rrt.h:143,166,228)
@@ -349,7 +343,7 @@ void launch_knn_grid(hipStream_t s, const GridView& g, const GridView* tg, const
 void launch_collide_poses(hipStream_t s, const EnvView& env, const RobotView& rob, const double* pos6, int n,
                           const int32_t* live_flags, uint8_t* hit, bool explicit_rt = false);
 
-// arguments of k_classify (one thread per sample of the round)
+// arguments of the round's query kernels, k_query_classify / k_query_block (one sample of the round each)
 struct ClassifyArgs {
   int n, N0, cap, nbcap, rank, world;
   int goal_id;              // store id of the goal node, -1 without a goal (src/forest.h:286-287)
@@ -362,8 +356,8 @@ struct ClassifyArgs {
                             // temporary store entry N0 + i either way
   const uint8_t* force;     // n (Node::ForceChildren of the expanded node)
   const int32_t* cnt;       // n sweep hit totals
-  int32_t* hit_idx;         // n x cap (reordered in place)
-  double* hit_dist;         // n x cap
+  int32_t* hit_idx;         // nothing reads these two (the hits stay in LDS); they keep the struct's layout, which is
+  double* hit_dist;         // part of the query kernels' by-value arguments: callers pass nullptr
   const int32_t* tree;      // store column (incl. the round's temporaries)
   const double* pos;        // store positions (incl. temporaries)
   int32_t* rec_flags;       // n: bit0 = evaluated here, bit1 = list overflow -> host path
@@ -401,7 +395,6 @@ struct SurvivorItem {       // 16 bytes
   int32_t chunk;
   unsigned long long mask;  // samples of the chunk that need the exact test
 };
-void launch_classify(hipStream_t s, const ClassifyArgs& a);
 // neighbour query + classification in one launch (one wavefront per sample): the hits never leave the wave
 // env != nullptr: with the fused clearance cull (a.items / a.pose_hit / a.ctrl[2]); the exact work is then done by
 // launch_collide_items
@@ -655,13 +648,12 @@ struct SeqArgs {
   // accepted, ThresholdMisses = none), nodes} - 8 ints, indexed by the launch's wave number; null = off
   int32_t* trace; int trace_cap;
 };
-// picks the instance from a.optimize, a.f.prio.n_heaps > 0 and a.f.goal_id >= 0 (every combination has one); hipSuccess
-hipError_t launch_seq_waves(hipStream_t s, const SeqArgs& a);
-// Forest batches (k_seq_waves_batch): n independent forests in one launch, workgroup b = one wavefront = members_dev[b]'s
-// loop.  All members of a launch are of one kind (optimize: SFF*; priority: the priority-frontier mode, f.prio.n_heaps > 0
-// in every member; goal: the single-goal mode, f.goal_id >= 0 in every member; both: priority + goal), lds = the
-// largest collide_lds_bytes(rob.n_tri, 1) among them.  Returns the first error of setting the kernel's attribute or of the
-// launch itself.
+// The loop's one entry (k_seq_waves_batch): n independent forests in one launch - a forest batch, or the single forest of
+// sffgpu_forest_run with n = 1 -, workgroup b = one wavefront = members_dev[b]'s loop; the arguments are read from device
+// memory.  All members of a launch are of one kind, which the caller names (Forest::seq_kind).  optimize: SFF*; priority:
+// the priority-frontier mode, f.prio.n_heaps > 0 in every member; goal: the single-goal mode, f.goal_id >= 0 in every
+// member; both: priority + goal.  lds = the largest collide_lds_bytes(rob.n_tri, 1) among the members.  Returns the first
+// error of setting the kernel's attribute or of the launch itself.
 hipError_t launch_seq_waves_batch(hipStream_t s, const SeqArgs* members_dev, int n, bool optimize, bool priority, bool goal, size_t lds);
 // ---- the same loop, SPECULATED over many wavefronts (round 6, k_spec_waves).  One wavefront computes an attempt in
 // ~10-15 us however idle the other 1 023 SIMDs are; but what an attempt of the NEXT waves will be is known in advance
@@ -675,7 +667,7 @@ hipError_t launch_seq_waves_batch(hipStream_t s, const SeqArgs* members_dev, int
 // nothing else.  The LEADER (workgroup 0) owns the forest: it walks the records in the reference's order - it recomputes
 // every pick itself and only takes a scenario's records when node, word position, iteration and node count agree with its
 // own state - applies counters, border events, the accepted node, the closed list / frontier erase and the termination
-// tests exactly like k_seq_waves, follows the tree by the outcome that really happened, and publishes the next step.
+// tests exactly like k_seq_waves_batch, follows the tree by the outcome that really happened, and publishes the next step.
 // Everything a worker reads of what the leader wrote in the same launch is stored write-through (`sc1`) and loaded `sc1`;
 // control block and records travel as 8-byte {value, step} granules, so no fence and no flag is needed.
 // SFF*: a chain of all-fail scenarios only (an accepted node's rewires change costs the later attempts would read).

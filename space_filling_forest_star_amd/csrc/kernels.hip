@@ -118,97 +118,6 @@ __global__ __launch_bounds__(256) void k_grid_insert(GridView g, NodeStoreView s
   grid_put(g, it);
 }
 
-__device__ __forceinline__ void grid_test(const GridItem& it, const SweepQuery& Q, int q, const NodeStoreView& st,
-                                          const double* __restrict__ qpos, int32_t* __restrict__ cnt,
-                                          int32_t* __restrict__ hit_idx, double* __restrict__ hit_dist, int cap) {
-  if (it.id >= Q.max_id) return;
-  if (Q.tree >= 0 ? it.tree != Q.tree : (Q.tree < -1 && it.tree == -2 - Q.tree)) return;
-  double qp[6];
-  for (int k = 0; k < 6; ++k) qp[k] = qpos[6 * (size_t)q + k];
-  const double d = dist6(it.p, qp);
-  if (d < Q.r) {
-    int slot = atomicAdd(&cnt[q], 1);
-    if (slot < cap) {
-      hit_idx[(size_t)q * cap + slot] = it.id;
-      hit_dist[(size_t)q * cap + slot] = d;
-    }
-  }
-}
-
-// One wavefront per query: the cells touched by the query ball's bounding box are dealt to the
-// lanes (27 cells for the planner's radius), each lane walks its cell's bucket; all lanes then
-// share the overflow list.  Same fp32 superset filter + exact fp64 re-test as the linear sweep.
-template <bool SPECULATE>
-__device__ __forceinline__ void grid_walk(const GridView& g, const SweepQuery& Q, int q, int lane, float rf,
-                                          const NodeStoreView& st, const double* __restrict__ qpos,
-                                          int32_t* __restrict__ cnt, int32_t* __restrict__ hit_idx,
-                                          double* __restrict__ hit_dist, int cap) {
-  const int lx = grid_coord(Q.x - rf, g.ox, g.inv_cell, g.nx), hx = grid_coord(Q.x + rf, g.ox, g.inv_cell, g.nx);
-  const int ly = grid_coord(Q.y - rf, g.oy, g.inv_cell, g.ny), hy = grid_coord(Q.y + rf, g.oy, g.inv_cell, g.ny);
-  const int lz = grid_coord(Q.z - rf, g.oz, g.inv_cell, g.nz), hz = grid_coord(Q.z + rf, g.oz, g.inv_cell, g.nz);
-  const int wx = hx - lx + 1, wy = hy - ly + 1, wz = hz - lz + 1;
-  const int total = wx * wy * wz;
-  for (int c0 = 0; c0 < total; c0 += 32) {   // (lane = index within the query's half-wave)
-    const int c = c0 + lane;
-    if (c < total) {
-      const int cx = lx + c % wx, cy = ly + (c / wx) % wy, cz = lz + c / (wx * wy);
-      const size_t cell = ((size_t)cz * g.ny + cy) * g.nx + cx;
-      // the first two items of the bucket are fetched together with its fill count (three independent loads
-      // in flight; most cells hold 0-2 nodes), the rest only when the count says they exist
-      const GridItem* items = g.items + cell * g.bk;
-      GridItem i0, i1;
-      int m;
-      if (SPECULATE) {   // node grid: most cells near a query hold a node or two
-        i0 = items[0];
-        i1 = g.bk > 1 ? items[1] : i0;
-        m = g.cnt[cell];
-      } else {           // the round's own grid is nearly empty: look at the count first
-        m = g.cnt[cell];
-        if (m > 0) i0 = items[0];
-        if (m > 1) i1 = items[1];
-      }
-      if (m > g.bk) m = g.bk;
-      if (m > 0) grid_test(i0, Q, q, st, qpos, cnt, hit_idx, hit_dist, cap);
-      if (m > 1) grid_test(i1, Q, q, st, qpos, cnt, hit_idx, hit_dist, cap);
-      if (m > 2) {
-        GridItem it[6];
-#pragma unroll
-        for (int j = 0; j < 6; ++j)
-          if (j + 2 < m) it[j] = items[j + 2];
-#pragma unroll
-        for (int j = 0; j < 6; ++j)
-          if (j + 2 < m) grid_test(it[j], Q, q, st, qpos, cnt, hit_idx, hit_dist, cap);
-      }
-    }
-  }
-  int no = g.ovf_cnt[0];
-  if (no > g.ovf_cap) no = g.ovf_cap;
-  for (int j = lane; j < no; j += 32) grid_test(g.ovf[j], Q, q, st, qpos, cnt, hit_idx, hit_dist, cap);
-}
-
-// One half-wavefront (32 lanes) per query: the cells touched by the query ball's bounding box are dealt to the
-// lanes (27 cells for the planner's radius), each lane walks its cell's bucket; all lanes then
-// share the overflow list.  Same fp32 superset filter + exact fp64 re-test as the linear sweep.  With tg the
-// same walk is repeated over the grid of the round's own samples (query i keeps the ids below its max_id).
-__global__ __launch_bounds__(256) void k_grid_query(GridView g, GridView tg, NodeStoreView st,
-                                                    const SweepQuery* __restrict__ queries,
-                                                    const double* __restrict__ qpos, int nq, int32_t* __restrict__ cnt,
-                                                    int32_t* __restrict__ hit_idx, double* __restrict__ hit_dist,
-                                                    int cap, const int32_t* __restrict__ dev_n) {
-  if (dev_n) {
-    if (dev_n[1]) return;
-    nq = dev_n[0];
-  }
-  const int q = blockIdx.x * 8 + (threadIdx.x >> 5);
-  const int lane = threadIdx.x & 31;
-  if (q >= nq) return;
-  const SweepQuery Q = queries[q];
-  if (!Q.active) return;
-  const float rf = sqrtf(Q.r2f) * 1.000001f;
-  grid_walk<true>(g, Q, q, lane, rf, st, qpos, cnt, hit_idx, hit_dist, cap);
-  if (tg.cnt) grid_walk<false>(tg, Q, q, lane, rf, st, qpos, cnt, hit_idx, hit_dist, cap);
-}
-
 // ------------------------------------------------------------------ exact k nearest
 // (TopK / topk_insert / topk_worst: kernels_dev.h)
 __global__ __launch_bounds__(256) void k_knn_linear(NodeStoreView st, int n_store, const KnnQuery* __restrict__ queries, int nq,
@@ -2024,7 +1933,7 @@ struct WorkItem {   // 64 bytes: one (edge, chunk of 64 samples) unit of collisi
   double step[3];   // (b - a) / parts: distance between two consecutive samples
 };
 
-// Edge tasks are written on the device (k_classify for the forest rounds, k_seg_prepare for host batches)
+// Edge tasks are written on the device (k_query_classify / k_query_block for the forest rounds, k_seg_prepare for host batches)
 // into a sparse slot table (seg_ns > 0 = live edge).  k_seg_compact turns the table into a dense list of
 // 64-byte (slot, chunk, ...) work items - one block-level scan and ONE atomic per block, because returning atomics on a
 // single word saturate near 90/us chip-wide and a per-item dequeue would cost more than the work itself.
@@ -2043,7 +1952,7 @@ __global__ __launch_bounds__(256) void k_seg_compact(const int32_t* __restrict__
   __shared__ int wsum[4];
   __shared__ int base_s;
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  if (tg.cnt) {   // housekeeping: the round's own grid has been read (k_grid_query), empty the cells it used
+  if (tg.cnt) {   // housekeeping: the round's own grid has been read (k_query_classify / k_query_block), empty the cells it used
     for (int t = blockIdx.x * 256 + threadIdx.x; t < n_temps; t += gridDim.x * 256) {
       const float x = tx[t];
       if (x == x) {
@@ -2326,105 +2235,18 @@ __global__ __launch_bounds__(256) void k_seg_prepare(const double* __restrict__ 
   ovf[i] = 0;
 }
 
-// ------------------------------------------------------------------ neighbour classification
-// One wavefront per sample of the round, lane = sweep hit.  Replays, for its sample, the part of the
-// reference's neighbour loop (src/forest.h:262-300) that decides WHICH edges have to be checked:
-// keeps the hits that satisfy one of the two distance conditions (:276, :283), ranks them in the
-// order the reference visits them (tree id, then distance, then index), cuts the list after the
-// first store neighbour of another tree (the loop returns there, :296-299) and writes the edge
-// tasks + their (edge, chunk) work items.
-__device__ __forceinline__ void emit_items(const ClassifyArgs& A, size_t slot) {
-  // the edge's sample count doubles as its "live" mark; the persistent edge kernel scans these
-  A.seg_ns[slot] = edge_samples(edge_parts(A.seg_a + 6 * slot, A.seg_b + 6 * slot));
-}
-
-__global__ __launch_bounds__(256) void k_classify(ClassifyArgs A) {
-  if (A.dev_n) {
-    if (A.dev_n[1]) return;
-    A.n = A.dev_n[0];
-  }
-  const int i = blockIdx.x * 4 + (threadIdx.x >> 6);
-  const int lane = threadIdx.x & 63;
-  if (i >= A.n) return;
-  const int stride = 1 + A.nbcap;
-  for (int k = lane; k < stride; k += 64) {
-    A.seg_ns[(size_t)i * stride + k] = -1;
-    A.first_hit[(size_t)i * stride + k] = 0x7fffffff;
-    A.seg_ovf[(size_t)i * stride + k] = 0;
-  }
-  int flags = 0, nnb = 0;
-  const bool mine_shard = A.world <= 1 || i % A.world == A.rank;
-  if (A.in_lim[i] && mine_shard) {
-    flags |= 1;
-    const int cnt = A.cnt[i];
-    if (cnt > A.cap) {
-      flags |= 2;
-    } else {
-      const int ex = A.parent[i];
-      const int mine = A.tree[ex];
-      const bool force = A.force[i] != 0;
-      const double pdist = A.pdist[i];
-      const bool have = lane < cnt;
-      const int id = have ? A.hit_idx[(size_t)i * A.cap + lane] : 0x7fffffff;
-      const double d = have ? A.hit_dist[(size_t)i * A.cap + lane] : 0.0;
-      const int t = have ? A.tree[id] : 0x7fffffff;
-      const bool same = t == mine;
-      bool q = false;
-      if (have) q = same ? (!force && d < pdist - SFFG_TOL)          // src/forest.h:276
-                         : (d < A.dist_tree - SFFG_TOL);             // src/forest.h:283
-      int rank = 0;
-      for (int j = 0; j < cnt; ++j) {   // (lanes >= cnt hold no hit)
-        const int tj = __shfl(t, j), idj = __shfl(id, j), qj = __shfl((int)q, j);
-        const double dj = __shfl(d, j);
-        if (qj && (tj < t || (tj == t && (dj < d || (dj == d && idj < id))))) ++rank;
-      }
-      int cut = (q && !same && id < A.N0) ? rank : 0x7fffffff;
-      for (int off = 32; off > 0; off >>= 1) {
-        const int o = __shfl_xor(cut, off);
-        cut = o < cut ? o : cut;
-      }
-      const bool keep = q && rank <= cut;
-      const int nkeep = __popcll(__ballot(keep));
-      if (nkeep > A.nbcap) {
-        flags |= 2;   // the host path redoes this sample with unbounded lists
-      } else {
-        nnb = nkeep;
-        const double* exp = A.pos + 6 * (size_t)ex;
-        const double* np = A.newpos + 6 * (size_t)i;
-        if (keep) {
-          A.rec_nb[(size_t)i * A.nbcap + rank] = id;
-          A.rec_meta[(size_t)i * A.nbcap + rank] = (t << 1) | (same ? 1 : 0);
-          const size_t slot = (size_t)i * stride + 1 + rank;
-          const double* nbp = A.pos + 6 * (size_t)id;
-          double* sa = A.seg_a + 6 * slot;
-          double* sb = A.seg_b + 6 * slot;
-          if (same) { for (int k = 0; k < 6; ++k) { sa[k] = nbp[k]; sb[k] = np[k]; } }                 // isPathFree(neighbour, newPoint) :276
-          else if (id == A.goal_id) { for (int k = 0; k < 6; ++k) { sa[k] = np[k]; sb[k] = nbp[k]; } } // isPathFree(newPoint, goal) :287
-          else { for (int k = 0; k < 6; ++k) { sa[k] = exp[k]; sb[k] = nbp[k]; } }                     // isPathFree(expanded, neighbour) :288
-          emit_items(A, slot);
-        }
-        if (lane == 0) {   // slot 0: isPathFree(expanded, newPoint)  (src/forest.h:246)
-          const size_t slot = (size_t)i * stride;
-          double* sa = A.seg_a + 6 * slot;
-          double* sb = A.seg_b + 6 * slot;
-          for (int k = 0; k < 6; ++k) { sa[k] = exp[k]; sb[k] = np[k]; }
-          emit_items(A, slot);
-        }
-      }
-    }
-  }
-  if (lane == 0) {
-    A.rec_flags[i] = flags;
-    A.rec_nnb[i] = nnb;
-  }
-}
-
 // ------------------------------------------------------------------ neighbour query + classification, fused
 // One wavefront per sample.  Candidates: the items of the grid cells the query ball touches (27 for the planner's
 // radius), in the node grid and - where its occupancy bit is set - in the round's own grid, flattened over the
 // lanes (lane = candidate, not lane = cell, so that a cell with several items costs no extra step), fp32 superset
 // filter, exact fp64 re-test of the survivors.  The hits are compacted with __ballot into the wave's LDS slice
-// (no atomics, no hit list in HBM) and classified right away exactly like k_classify does.
+// (no atomics, no hit list in HBM) and classified right away, lane = hit.
+// The classification rule (the one description; k_query_block and the one-slot loops refer here): replay, for the
+// sample, the part of the reference's neighbour loop (src/forest.h:262-300) that decides WHICH edges have to be
+// checked.  Keep the hits that satisfy one of the two distance conditions (:276, :283), rank them in the order the
+// reference visits them (tree id, then distance, then index), cut the list after the first store neighbour of
+// another tree (the loop returns there, :296-299) and write the edge tasks; an edge's sample count (seg_ns) doubles
+// as its "live" mark for the edge kernels.
 #define QC_WAVES 4
 // A sample with more than 64 hits (the round's samples crowd together: priority-frontier mode, forests that fill the
 // angular dimensions) cannot rank them with one lane per hit.  Its grid scan is then run a second time with this
@@ -2647,7 +2469,7 @@ __global__ __launch_bounds__(64 * QC_WAVES) __attribute__((amdgpu_waves_per_eu(Q
     if (no_t > 0) qc_overflow(tg, no_t, lane, Q, qp, h_id, h_d, h_tree, h_pos, nh, top);
     };
     scan(nullptr);
-    // ---- classification (k_classify's logic on the wave's own hit list)
+    // ---- classification (the rule above this kernel, on the wave's own hit list)
     qt1 = DBG_T();
     int cnt = nh;
     // more hits than lanes (and no test asks for a smaller list): the scan again, keeping the first QC_TOP qualifying hits
@@ -2903,7 +2725,7 @@ __global__ __launch_bounds__(64 * QC_WAVES) __attribute__((amdgpu_waves_per_eu(Q
 //      list; beside it lane = one group of eight samples of the parent edges' first four chunks: clearance bit requested
 //   2  lane = entry of the second work list (rare), the grids' overflow lists
 //   3  lane = candidate: authoritative fp64 position from the store, exact distance -> per-sample hit lists
-//   4  lane = (sample, hit): classification (k_classify's logic: rank by a loop over the sample's hits in LDS, the cut
+//   4  lane = (sample, hit): classification (the rule above k_query_classify: rank by a loop over the sample's hits in LDS, the cut
 //      by an LDS atomicMin), neighbour records, the kept edges' cull rows
 //   5  lane = edge task: its 64-sample chunks -> (task, chunk) pair table
 //   6  lane = one group of eight samples of a pair: clearance bit -> masks -> survivors (LDS, one pair of atomics per
@@ -3242,7 +3064,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(QB_OCC))) v
   }
   __syncthreads();
   QB_MARK(4);
-  // ---- 4. classification (k_classify's logic), lane = hit: 16 lanes per sample when no sample of the workgroup has more
+  // ---- 4. classification (the rule above k_query_classify), lane = hit: 16 lanes per sample when no sample of the workgroup has more
   // than 16 hits (the usual case: ~5) - two wavefronts do the pass, the other two skip it -, else 32 lanes per sample
   int gsh = 4;
   for (int q = 0; q < S; ++q) if (s_nhit[q] > 16) gsh = 5;
@@ -4113,7 +3935,7 @@ __device__ __forceinline__ void sq_edges_clear_probe(const EnvView& env, const d
 __device__ __attribute__((noinline)) bool sq_path_free(const EnvView& env, const RobotView& rob, const double* rtri, int32_t* stack, int32_t* cand, int32_t* queue,
                              double* stage, const double* a, const double* b, int32_t* fh_lds, int32_t* ovf_lds, int lane,
                              unsigned long long& calls, unsigned long long& samples, bool& fault) {
-  const double* rbox = reinterpret_cast<const double*>(queue + QUEUE_CAP);   // (k_seq_waves: one wave, the boxes lie behind its queue)
+  const double* rbox = reinterpret_cast<const double*>(queue + QUEUE_CAP);   // (k_seq_waves_batch: one wave, the boxes lie behind its queue)
   const double parts = edge_parts(a, b);
   const int ns = edge_samples(parts);
   samples += (unsigned long long)ns;
@@ -4401,13 +4223,8 @@ static hipError_t set_dyn_lds(K kernel, size_t lds, size_t threshold) {
   return hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
 }
 
-// the loop itself is seq_waves_body.inc.  k_seq_waves includes it as text, on its by-value argument, which keeps this entry's
-// code as it was before the loop was shared; seq_waves_body is the same loop as a function of a reference (k_seq_waves_batch)
-template <bool OPT, bool PRIO, bool GOAL>
-__global__ __launch_bounds__(64) void k_seq_waves(SeqArgs A) {
-#include "seq_waves_body.inc"
-}
-
+// the loop itself is seq_waves_body.inc: the body of this one function of a reference to the forest's arguments, which
+// k_seq_waves_batch - the loop's only entry, for one forest as for many - calls on its workgroup's member
 template <bool OPT, bool PRIO, bool GOAL>
 __device__ __forceinline__ void seq_waves_body(const SeqArgs& A) {
 #include "seq_waves_body.inc"
@@ -4415,7 +4232,7 @@ __device__ __forceinline__ void seq_waves_body(const SeqArgs& A) {
 
 // Forest batches: workgroup b (one wavefront) runs the loop of members[b], an independent forest with a store, a grid, a
 // ring and a control block of its own.  The member's arguments are read through the uniform pointer, never copied into a
-// local, so they live in scalar registers like the kernel arguments of k_seq_waves do.  A workgroup never waits for another
+// local, so they live in scalar registers like kernel arguments do.  A workgroup never waits for another
 // one - no step word, no records, no barrier across the grid - so, unlike k_spec_waves, no grid size can strand a workgroup:
 // what is not resident at once simply runs when a slot frees up.
 template <bool OPT, bool PRIO, bool GOAL>
@@ -4441,21 +4258,6 @@ hipError_t launch_seq_waves_batch(hipStream_t s, const SeqArgs* members_dev, int
 
 #include "rrt_seq_batch.inc"
 #include "smooth_paths.inc"
-
-template <bool OPT, bool PRIO, bool GOAL>
-static void launch_seq_waves_as(hipStream_t s, const SeqArgs& a, size_t lds) {
-  (void)set_dyn_lds(k_seq_waves<OPT, PRIO, GOAL>, lds, 48 * 1024);
-  hipLaunchKernelGGL((k_seq_waves<OPT, PRIO, GOAL>), dim3(1), dim3(64), lds, s, a);
-}
-hipError_t launch_seq_waves(hipStream_t s, const SeqArgs& a) {
-  const size_t lds = collide_lds_bytes(a.rob.n_tri, 1);
-  if (a.f.goal_id >= 0 && a.f.prio.n_heaps > 0) { if (a.optimize) launch_seq_waves_as<true, true, true>(s, a, lds); else launch_seq_waves_as<false, true, true>(s, a, lds); }
-  else if (a.f.goal_id >= 0) { if (a.optimize) launch_seq_waves_as<true, false, true>(s, a, lds); else launch_seq_waves_as<false, false, true>(s, a, lds); }
-  else if (a.f.prio.n_heaps > 0) { if (a.optimize) launch_seq_waves_as<true, true, false>(s, a, lds); else launch_seq_waves_as<false, true, false>(s, a, lds); }
-  else if (a.optimize) launch_seq_waves_as<true, false, false>(s, a, lds);
-  else launch_seq_waves_as<false, false, false>(s, a, lds);
-  return hipSuccess;
-}
 
 // ------------------------------------------------------------------ waves of one slot, SPECULATED (kernels.h: SpecArgs)
 // (wt_*, the write-through stores for what the leader writes and a worker on another XCD reads in the same launch: kernels_dev.h)
@@ -4832,18 +4634,11 @@ __global__ __launch_bounds__(OPT ? 192 : 128) void k_spec_waves(SpecArgs S) {
           if (s_row[SPG_EVENT]) {                // :288-294 border entry unless the pair has one
             const int s_id = (int)s_row[SPG_EV_ID], s_tree = (int)s_row[SPG_EV_TREE];
             const int a = s_id < node ? s_id : node, b = s_id < node ? node : s_id;
-            const unsigned long long key = ((unsigned long long)(uint32_t)a << 32) | ((unsigned long long)(uint32_t)b + 1ULL);
-            size_t h = (size_t)((key * 0x9E3779B97F4A7C15ULL) >> 17) & (size_t)f.bt_mask;
-            bool fresh = false;
+            const unsigned long long key = border_key(a, b);
+            size_t h;
             // (the table is the leader's alone while the launch runs - written by this wavefront, read through its own CU's
             // caches: plain loads, no round trip to memory per probe)
-            for (int guard = 0; guard < (1 << 24); ++guard) {
-              const unsigned long long cur = f.bt_key[h];
-              if (cur == key) { fresh = f.bt_val[h] == ~0ULL; break; }
-              if (cur == 0ULL) { fresh = true; break; }
-              h = (h + 1) & (size_t)f.bt_mask;
-            }
-            if (fresh) {
+            if (border_probe<false>(f, key, h)) {
               if (lane == 0) {
                 f.bt_key[h] = key;
                 f.bt_val[h] = epoch << 32;
@@ -4897,18 +4692,8 @@ __global__ __launch_bounds__(OPT ? 192 : 128) void k_spec_waves(SpecArgs S) {
         // ---- termination (:184-201)
         empty_frontier = fn == 0 ? 1 : 0;
         if (!solved && empty_frontier) {
-          unsigned long long reach = 1ULL, frontier_set = 1ULL;
-          if (R <= 64) {
-            unsigned long long row = 0ULL;   // lane a: bit b = pair (a, b) has a border
-            if (lane < R) for (int b2 = 0; b2 < R; ++b2) if (sq_u8(f.pair + (size_t)lane * R + b2)) row |= 1ULL << b2;
-            while (frontier_set) {
-              const int a = __ffsll((long long)frontier_set) - 1;
-              frontier_set &= frontier_set - 1;
-              const unsigned long long ra = __shfl(row, a) & ~reach;
-              reach |= ra; frontier_set |= ra;
-            }
-            solved = __popcll(reach) == R ? 1 : 0;
-          } else fault = SFFK_FAULT_LISTS;
+          if (R <= 64) solved = trees_connected(f.pair, R, lane) ? 1 : 0;   // maxConnected() == numRoots
+          else fault = SFFK_FAULT_LISTS;
         }
         const bool budget = f.node_budget > 0 && n_nodes >= f.node_budget;
         terminated = (solved || iter >= f.max_iterations || budget) ? 1 : 0;
@@ -4982,24 +4767,12 @@ __global__ __launch_bounds__(OPT ? 192 : 128) void k_spec_waves(SpecArgs S) {
       if (wv == 1) {
         // the neighbours: exact 6-D ball of radius max(parentDistance, treeDistance) from the cells its box touches (:262-267)
         const double r = pdist > A.dist_tree ? pdist : A.dist_tree;
-        const double ri = (r + A.sweep_abs_eps) * (1.0 + 1e-5);
-        const float rf = sqrtf((float)(ri * ri) * 1.000001f) * 1.000001f;
-        const GridView& g = A.g;
-        const float qx = (float)qp[0], qy = (float)qp[1], qz = (float)qp[2];
-        const int lx = grid_coord(qx - rf, g.ox, g.inv_cell, g.nx), hx = grid_coord(qx + rf, g.ox, g.inv_cell, g.nx);
-        const int ly = grid_coord(qy - rf, g.oy, g.inv_cell, g.ny), hy = grid_coord(qy + rf, g.oy, g.inv_cell, g.ny);
-        const int lz = grid_coord(qz - rf, g.oz, g.inv_cell, g.nz), hz = grid_coord(qz + rf, g.oz, g.inv_cell, g.nz);
-        const int wx = hx - lx + 1, wy = hy - ly + 1, wz = hz - lz + 1;
-        const int total = wx * wy * wz;
-        auto take = [&](bool vld, const GridItem* src) {        // one candidate per lane -> the hit list in LDS
+        grid_ball_items(A.g, qp, ball_box_radius(r, A.sweep_abs_eps), lane, [&](bool vld, const GridItem* src) {   // one candidate per lane -> the hit list in LDS
           bool h = false;
           double d = 0, p6[6];
           int id = 0, tr = 0;
           if (vld) {
-            const unsigned long long* q8 = reinterpret_cast<const unsigned long long*>(src);
-            for (int k = 0; k < 6; ++k) p6[k] = __longlong_as_double((long long)sq_u64(q8 + k));
-            const unsigned long long it = sq_u64(q8 + 6);
-            id = (int)(unsigned)(it & 0xffffffffULL); tr = (int)(unsigned)(it >> 32);
+            grid_item_load(src, p6, id, tr);
             d = dist6(p6, qp);
             h = d < r && id < nn0;                               // (a node the leader commits while this step runs reaches the attempt through its scenario)
           }
@@ -5009,38 +4782,7 @@ __global__ __launch_bounds__(OPT ? 192 : 128) void k_spec_waves(SpecArgs S) {
             if (at < 64) { h_id[at] = id; h_tree[at] = tr; h_d[at] = d; for (int k = 0; k < 6; ++k) h_pos[6 * at + k] = p6[k]; }
           }
           n_hit += __popcll(hm);
-        };
-        for (int c0 = 0; c0 < total; c0 += 64) {
-          const int ci = c0 + lane;
-          int cell = 0, m = 0;
-          if (ci < total) {
-            const int q1 = ci / wx, q2 = q1 / wy;
-            cell = ((lz + q2) * g.ny + (ly + q1 - q2 * wy)) * g.nx + (lx + ci - q1 * wx);
-            m = sq_i32(g.cnt + cell);
-            if (m > g.bk) m = g.bk;
-          }
-          int inc = m;
-          for (int off = 1; off < 64; off <<= 1) {
-            const int o = __shfl_up(inc, off);
-            if (lane >= off) inc += o;
-          }
-          const int tot = __shfl(inc, 63);
-          for (int base = 0; base < tot; base += 64) {
-            const int j = base + lane;
-            const int jj = j < tot ? j : tot - 1;
-            int lo = 0, hi = 63;
-            while (lo < hi) {
-              const int mid = (lo + hi) >> 1;
-              if (__shfl(inc, mid) > jj) hi = mid; else lo = mid + 1;
-            }
-            const int src_cell = __shfl(cell, lo);
-            const int slot2 = jj - (__shfl(inc, lo) - __shfl(m, lo));
-            take(j < tot, g.items + (size_t)src_cell * g.bk + slot2);
-          }
-        }
-        int no = sq_i32(g.ovf_cnt);
-        if (no > g.ovf_cap) no = g.ovf_cap;
-        for (int base = 0; base < no; base += 64) take(base + lane < no, g.ovf + base + lane);
+        });
       }
       if (wv == 1) {
         __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
@@ -5189,7 +4931,7 @@ __global__ __launch_bounds__(OPT ? 192 : 128) void k_spec_waves(SpecArgs S) {
     int status = SPS_REJECT;
     if (!valid) status = SPS_INVALID;
     else if (iter_a >= f.max_iterations) status = SPS_SKIPPED;
-    // ---- the attempt (k_seq_waves's, without its writes)
+    // ---- the attempt (k_seq_waves_batch's, without its writes)
     unsigned long long cc_l = 0;
     int pf_l = 0, nq_l = 0, event = 0, ev_id = 0, ev_tree = 0, mine = 0, par_new = node, n_rw = 0, n_mem = 0;
     double ev_dist = 0, pdist = 0, best = 0, dcl_new = 0, qp[6] = {0, 0, 0, 0, 0, 0};
@@ -5333,12 +5075,7 @@ __global__ __launch_bounds__(OPT ? 192 : 128) void k_spec_waves(SpecArgs S) {
             const double d = have ? h_d[lane] : 0.0;
             const bool same = t == mine;
             const bool qk = have && (same ? (!force && d < pdist - SFFG_TOL) : (d < A.dist_tree - SFFG_TOL));   // :276 / :283
-            int rank = 0;
-            for (int j = 0; j < n_hit; ++j) {
-              const int tj = __shfl(t, j), idj = __shfl(id, j), qj = __shfl((int)qk, j);
-              const double dj = __shfl(d, j);
-              if (qj && (tj < t || (tj == t && (dj < d || (dj == d && idj < id))))) ++rank;
-            }
+            const int rank = nb_rank(n_hit, t, d, id, qk);
             const int n_q = __popcll(__ballot(qk));
             for (int rk = 0; rk < n_q && !reject && !flt && !aborted; ++rk) {
               const unsigned long long sel = __ballot(qk && rank == rk);
@@ -5774,14 +5511,6 @@ void launch_grid_insert(hipStream_t s, const GridView& g, const NodeStoreView& s
   if (n <= 0) return;
   hipLaunchKernelGGL(k_grid_insert, dim3((n + 255) / 256), dim3(256), 0, s, g, st, first, n);
 }
-void launch_grid_query(hipStream_t s, const GridView& g, const GridView* tg, const NodeStoreView& st,
-                       const SweepQuery* queries, const double* qpos, int nq, int32_t* cnt, int32_t* hit_idx,
-                       double* hit_dist, int cap, const int32_t* dev_n) {
-  if (nq <= 0) return;
-  GridView none{};
-  hipLaunchKernelGGL(k_grid_query, dim3((nq + 7) / 8), dim3(256), 0, s, g, tg ? *tg : none, st, queries, qpos, nq, cnt,
-                     hit_idx, hit_dist, cap, dev_n);
-}
 void launch_knn_linear(hipStream_t s, const NodeStoreView& st, int n_store, const KnnQuery* q, int nq, int kcap,
                        int32_t* idx, double* dist, int32_t* cnt, double abs_eps) {
   if (nq <= 0) return;
@@ -5930,11 +5659,6 @@ void launch_star_tail(hipStream_t s, const ResolveArgs& a, const EnvView& env, c
   const int cap = wgs_bound > 0 ? std::min(wgs_bound, cus) : cus;
   const int blocks = std::max(1, std::min(cap, std::max(16, (n_bound + 3) / 4)));
   hipLaunchKernelGGL(k_star_tail, dim3(blocks), dim3(64 * SEG_WAVES), lds, s, a, env, rob, st, max_passes, test_stall);
-}
-
-void launch_classify(hipStream_t s, const ClassifyArgs& a) {
-  if (a.n <= 0) return;
-  hipLaunchKernelGGL(k_classify, dim3((a.n + 3) / 4), dim3(256), 0, s, a);
 }
 
 void launch_seg_gather(hipStream_t s, const double* store_pos, const int32_t* ida, const int32_t* idb, int n, double* a6,

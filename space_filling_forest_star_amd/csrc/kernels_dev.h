@@ -62,6 +62,113 @@ __device__ __forceinline__ void wt_f64(double* p, double v) {
 }
 __device__ __forceinline__ void wt_u8(uint8_t* p, uint8_t v) { __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
 
+// ---- the idioms of the one-slot loops (seq_waves_body.inc, k_spec_waves, rrt_seq_batch.inc): ONE wavefront works for one
+// attempt, all 64 lanes together.  The round kernels and sq_knn keep their own copies of the flattening below
+// (qc_candidates, collect_from_grid, knn_cells, star_cells_mates ...): helpers cost time there, profiles/README.md
+// ("Shared idioms") has the numbers.
+// fp32 half-edge of the cell box around an exact fp64 ball of radius r: the store's fp32 slack and a few ulps on top
+__device__ __forceinline__ float ball_box_radius(double r, double sweep_abs_eps) {
+  const double ri = (r + sweep_abs_eps) * (1.0 + 1e-5);
+  return sqrtf((float)(ri * ri) * 1.000001f) * 1.000001f;
+}
+// an item of the node grid: its fp64 position, id and tree (the launch itself writes items, hence sq loads)
+__device__ __forceinline__ void grid_item_load(const GridItem* src, double* p6, int& id, int& tree) {
+  const unsigned long long* q8 = reinterpret_cast<const unsigned long long*>(src);
+  for (int k = 0; k < 6; ++k) p6[k] = __longlong_as_double((long long)sq_u64(q8 + k));
+  const unsigned long long w = sq_u64(q8 + 6);
+  id = (int)(unsigned)(w & 0xffffffffULL); tree = (int)(unsigned)(w >> 32);
+}
+// The neighbour ball: every item of the cells the box of half-edge rf around qp touches, then the overflow list.  64
+// cells at a time (lane = cell) give their fill counts; a prefix scan and a six-step bisection deal the items over the
+// lanes (lane = item), so that a cell with several items costs no extra step.  take(valid, item) is called by all 64
+// lanes together (it may __ballot); valid = this lane has an item.
+template <class Take>
+__device__ __forceinline__ void grid_ball_items(const GridView& g, const double* qp, float rf, int lane, Take&& take) {
+  const float qx = (float)qp[0], qy = (float)qp[1], qz = (float)qp[2];
+  const int lx = grid_coord(qx - rf, g.ox, g.inv_cell, g.nx), hx = grid_coord(qx + rf, g.ox, g.inv_cell, g.nx);
+  const int ly = grid_coord(qy - rf, g.oy, g.inv_cell, g.ny), hy = grid_coord(qy + rf, g.oy, g.inv_cell, g.ny);
+  const int lz = grid_coord(qz - rf, g.oz, g.inv_cell, g.nz), hz = grid_coord(qz + rf, g.oz, g.inv_cell, g.nz);
+  const int wx = hx - lx + 1, wy = hy - ly + 1, wz = hz - lz + 1;
+  const int total = wx * wy * wz;
+  for (int c0 = 0; c0 < total; c0 += 64) {
+    const int ci = c0 + lane;
+    int cell = 0, m = 0;
+    if (ci < total) {
+      const int q1 = ci / wx, q2 = q1 / wy;
+      cell = ((lz + q2) * g.ny + (ly + q1 - q2 * wy)) * g.nx + (lx + ci - q1 * wx);
+      m = sq_i32(g.cnt + cell);
+      if (m > g.bk) m = g.bk;
+    }
+    int inc = m;
+    for (int off = 1; off < 64; off <<= 1) {
+      const int o = __shfl_up(inc, off);
+      if (lane >= off) inc += o;
+    }
+    const int tot = __shfl(inc, 63);
+    for (int base = 0; base < tot; base += 64) {
+      const int j = base + lane;
+      const int jj = j < tot ? j : tot - 1;
+      int lo = 0, hi = 63;
+      while (lo < hi) {
+        const int mid = (lo + hi) >> 1;
+        if (__shfl(inc, mid) > jj) hi = mid; else lo = mid + 1;
+      }
+      const int src_cell = __shfl(cell, lo);
+      const int slot = jj - (__shfl(inc, lo) - __shfl(m, lo));
+      take(j < tot, g.items + (size_t)src_cell * g.bk + slot);
+    }
+  }
+  int no = sq_i32(g.ovf_cnt);
+  if (no > g.ovf_cap) no = g.ovf_cap;
+  for (int base = 0; base < no; base += 64) take(base + lane < no, g.ovf + base + lane);
+}
+// The neighbour rank: lane j < n_hit holds hit j (tree t, distance d, id; qk = it qualifies as a neighbour); the number
+// of qualifying hits the reference's neighbour loop visits before this lane's: tree id, then distance, then id
+__device__ __forceinline__ int nb_rank(int n_hit, int t, double d, int id, bool qk) {
+  int rank = 0;
+  for (int j = 0; j < n_hit; ++j) {
+    const int tj = __shfl(t, j), idj = __shfl(id, j), qj = __shfl((int)qk, j);
+    const double dj = __shfl(d, j);
+    if (qj && (tj < t || (tj == t && (dj < d || (dj == d && idj < id))))) ++rank;
+  }
+  return rank;
+}
+// The border table (DevForestView::bt_key / bt_val, open addressing): the key of the node pair a < b (never 0), where its
+// probe sequence starts, and the read-only probe - h = the slot that holds the key or the first free one, true = the pair
+// has no live entry (the caller may then write one at h).  SQ: sq loads, for a table other launches' or wavefronts' stores
+// may have filled; plain loads where the table is the wavefront's alone while the launch runs.
+__device__ __forceinline__ unsigned long long border_key(int a, int b) {
+  return ((unsigned long long)(uint32_t)a << 32) | ((unsigned long long)(uint32_t)b + 1ULL);
+}
+__device__ __forceinline__ size_t border_hash(const DevForestView& f, unsigned long long key) {
+  return (size_t)((key * 0x9E3779B97F4A7C15ULL) >> 17) & (size_t)f.bt_mask;
+}
+template <bool SQ>
+__device__ __forceinline__ bool border_probe(const DevForestView& f, unsigned long long key, size_t& h) {
+  h = border_hash(f, key);
+  for (int guard = 0; guard < (1 << 24); ++guard) {
+    const unsigned long long cur = SQ ? sq_u64(f.bt_key + h) : f.bt_key[h];
+    if (cur == key) return (SQ ? sq_u64(f.bt_val + h) : f.bt_val[h]) == ~0ULL;
+    if (cur == 0ULL) return true;
+    h = (h + 1) & (size_t)f.bt_mask;
+  }
+  return false;
+}
+// The connected-trees test, maxConnected() == numRoots: every tree is reachable from tree 0 over pairs that hold a border
+// (pair: R x R flags).  A lane per tree: R <= 64.
+__device__ __forceinline__ bool trees_connected(const uint8_t* pair, int R, int lane) {
+  unsigned long long reach = 1ULL, frontier_set = 1ULL;
+  unsigned long long row = 0ULL;   // lane a: bit b = pair (a, b) has a border
+  if (lane < R) for (int b2 = 0; b2 < R; ++b2) if (sq_u8(pair + (size_t)lane * R + b2)) row |= 1ULL << b2;
+  while (frontier_set) {
+    const int a = __ffsll((long long)frontier_set) - 1;
+    frontier_set &= frontier_set - 1;
+    const unsigned long long ra = __shfl(row, a) & ~reach;
+    reach |= ra; frontier_set |= ra;
+  }
+  return __popcll(reach) == R;
+}
+
 // libstdc++ uniform_int_distribution<int>(0, range - 1) on one 64-bit engine word (Lemire's multiply-shift):
 // returns the draw, or -1 when the word falls into the rejection zone (the reference then draws again)
 __device__ __forceinline__ int lemire_pick(unsigned long long word, unsigned long long range) {

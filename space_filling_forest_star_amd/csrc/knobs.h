@@ -42,12 +42,12 @@ struct Knobs {
   bool prio_device = true;          // SFFGPU_PRIO_DEVICE=0: priority-frontier mode stays on the host-replay engine
   bool prio_seq = false;            // SFFGPU_PRIO_SEQ=1 (tests): picks by the sequential k_prio_begin instead of k_prio_plan
   bool prio_loop = false;           // SFFGPU_PRIO_LOOP=1: a priority-frontier forest without a goal of waves of ONE slot runs on the device, in the
-                                    // single-wavefront loop (k_seq_waves<., true>), and may be a member of a forest batch; 0 = the host-replay engine
+                                    // single-wavefront loop (k_seq_waves_batch<., true>), and may be a member of a forest batch; 0 = the host-replay engine
   bool goal_loop = false;           // SFFGPU_GOAL_LOOP=1: a single-goal forest (has_goal, no priority frontier) of waves of ONE slot runs in the
-                                    // single-wavefront loop (k_seq_waves<., false, true>) and may be a member of a forest batch; 0 = the round engine,
+                                    // single-wavefront loop (k_seq_waves_batch<., false, true>) and may be a member of a forest batch; 0 = the round engine,
                                     // the solving wave replayed on the host
   bool prio_goal_loop = false;      // SFFGPU_PRIO_GOAL_LOOP=1: a forest with BOTH a goal and a priority bias (one heap per start tree, keyed by the distance
-                                    // to the goal) of waves of ONE slot runs in the single-wavefront loop (k_seq_waves<., true, true>) and may be a member
+                                    // to the goal) of waves of ONE slot runs in the single-wavefront loop (k_seq_waves_batch<., true, true>) and may be a member
                                     // of a forest batch; 0 = the host-replay engine.  Neither prio_loop nor goal_loop covers the combination
   bool no_order = false;            // SFFGPU_NO_ORDER=1: a round's samples by index instead of in the wave's spatial order (sffk::OrderView)
   int order_min_wave = 4096;        // SFFGPU_ORDER_MIN_WAVE (>= 2): smallest wave that uses the order
@@ -70,8 +70,8 @@ struct Knobs {
   int kc_trace = -1;                // SFFGPU_KC_TRACE=<round>: that round's k_commit timeline with SFFGPU_PROFILE (-1 = off)
   bool digest = false;              // SFFGPU_DIGEST (set at all): the host-replay engine prints every round's answers
   // waves of one slot
-  bool no_seq = false;              // SFFGPU_NO_SEQ=1: through the round engine instead of k_seq_waves / k_spec_waves
-  bool spec = true;                 // SFFGPU_SPEC=0: the single wavefront (k_seq_waves) instead of the speculative kernel
+  bool no_seq = false;              // SFFGPU_NO_SEQ=1: through the round engine instead of k_seq_waves_batch / k_spec_waves
+  bool spec = true;                 // SFFGPU_SPEC=0: the single wavefront (k_seq_waves_batch) instead of the speculative kernel
   int spec_depth = 0;               // SFFGPU_SPEC_DEPTH: waves per step (0 = 3, the tree; SFF*: 4, the chain)
   int spec_sets = 1;                // SFFGPU_SPEC_SETS: sets of workers that take the steps in turn
   bool spec_pipe = true;            // SFFGPU_SPEC_PIPE=0: write a step's nodes before the next one is published

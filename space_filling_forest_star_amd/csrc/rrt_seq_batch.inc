@@ -173,27 +173,16 @@ __device__ __forceinline__ void rrt_seq_body(const RrtSeqArgs& A) {
     if constexpr (!LAZY) if (n_live > 1) {
       nq += (unsigned long long)(n_live - 1);
       const double r = A.dist_tree;
-      const double ri = (r + A.sweep_abs_eps) * (1.0 + 1e-5);
-      const float rf = sqrtf((float)(ri * ri) * 1.000001f) * 1.000001f;
-      const float qx = (float)qp[0], qy = (float)qp[1], qz = (float)qp[2];
-      const int lx = grid_coord(qx - rf, g.ox, g.inv_cell, g.nx), hx = grid_coord(qx + rf, g.ox, g.inv_cell, g.nx);
-      const int ly = grid_coord(qy - rf, g.oy, g.inv_cell, g.ny), hy = grid_coord(qy + rf, g.oy, g.inv_cell, g.ny);
-      const int lz = grid_coord(qz - rf, g.oz, g.inv_cell, g.nz), hz = grid_coord(qz + rf, g.oz, g.inv_cell, g.nz);
-      const int wx = hx - lx + 1, wy = hy - ly + 1, wz = hz - lz + 1;
-      const int total = wx * wy * wz;
       double bd = 1.0e300;         // lane i: the nearest node of live tree i seen so far, and whether another one ties with it
       int bid = 0x7fffffff;
       bool btie = false;
-      auto take = [&](bool valid, const GridItem* src) {        // one candidate per lane -> the lane of its tree
+      grid_ball_items(g, qp, ball_box_radius(r, A.sweep_abs_eps), lane, [&](bool valid, const GridItem* src) {   // one candidate per lane -> the lane of its tree
         bool h = false;
         double d = 0;
         int id = 0, tr = 0;
         if (valid) {
-          const unsigned long long* q8 = reinterpret_cast<const unsigned long long*>(src);
           double p6[6];
-          for (int k = 0; k < 6; ++k) p6[k] = __longlong_as_double((long long)sq_u64(q8 + k));
-          const unsigned long long w = sq_u64(q8 + 6);
-          id = (int)(unsigned)(w & 0xffffffffULL); tr = (int)(unsigned)(w >> 32);
+          grid_item_load(src, p6, id, tr);
           d = dist6(p6, qp);
           h = tr != mine && d < r;                               // :231 (no TOLERANCE here)
         }
@@ -208,38 +197,7 @@ __device__ __forceinline__ void rrt_seq_body(const RrtSeqArgs& A) {
             if (key_less(sd, sid, bd, bid)) { if (sd < bd) btie = false; bd = sd; bid = sid; }
           }
         }
-      };
-      for (int c0 = 0; c0 < total; c0 += 64) {
-        const int ci = c0 + lane;
-        int cell = 0, m = 0;
-        if (ci < total) {
-          const int q1 = ci / wx, q2 = q1 / wy;
-          cell = ((lz + q2) * g.ny + (ly + q1 - q2 * wy)) * g.nx + (lx + ci - q1 * wx);
-          m = sq_i32(g.cnt + cell);
-          if (m > g.bk) m = g.bk;
-        }
-        int inc = m;
-        for (int off = 1; off < 64; off <<= 1) {
-          const int o = __shfl_up(inc, off);
-          if (lane >= off) inc += o;
-        }
-        const int tot = __shfl(inc, 63);
-        for (int base = 0; base < tot; base += 64) {
-          const int j = base + lane;
-          const int jj = j < tot ? j : tot - 1;
-          int lo = 0, hi = 63;
-          while (lo < hi) {
-            const int mid = (lo + hi) >> 1;
-            if (__shfl(inc, mid) > jj) hi = mid; else lo = mid + 1;
-          }
-          const int src_cell = __shfl(cell, lo);
-          const int slot = jj - (__shfl(inc, lo) - __shfl(m, lo));
-          take(j < tot, g.items + (size_t)src_cell * g.bk + slot);
-        }
-      }
-      int no = sq_i32(g.ovf_cnt);
-      if (no > g.ovf_cap) no = g.ovf_cap;
-      for (int base = 0; base < no; base += 64) take(base + lane < no, g.ovf + base + lane);
+      });
       // the trees that have a node in the ball, in frontier order (:219): tie -> host, edge (:231), free -> link + merge -> host
       unsigned long long todo = __ballot(bid != 0x7fffffff);
       int why = 0;

@@ -1,12 +1,9 @@
-// seq_waves_body.inc - the loop of ONE forest of waves of one slot on ONE wavefront (kernels.h: SeqArgs), as text over `A`:
-// kernels.hip includes it in k_seq_waves<OPT> (`A` = the kernel's by-value argument) and in seq_waves_body<OPT> (`A` = a
-// reference; k_seq_waves_batch calls it on the workgroup's member of the argument array).  The single-forest entry includes
-// the text instead of calling the function because the call, inlined, changed the register allocation of its SFF* instance
-// (310 -> 536 scalar spills, - 3.6 % on its loop, measured); included, both its instances compiled, when the batch entry
-// came in, to exactly what they had been before it.
-// The batch entry is the other way round: through the function its SFF* instance spills 366 scalars, as included text 517
+// seq_waves_body.inc - the loop of ONE forest of waves of one slot on ONE wavefront (kernels.h: SeqArgs): the body of
+// seq_waves_body<OPT, PRIO, GOAL>(const SeqArgs& A) in kernels.hip, included there once.  k_seq_waves_batch, the loop's only
+// entry, calls it on the workgroup's member of the argument array; a single forest is a batch of one.  It stays a function
+// the kernel calls, not text in the kernel: through the function the SFF* instance spills 366 scalars, as included text 517
 // (- 11 %, measured).  Nothing in here looks at the workgroup's index.
-// lemire_pick and the sq_* loads are kernels_dev.h's.
+// lemire_pick, the sq_* loads and the one-slot idioms (grid_ball_items, nb_rank, border_*, trees_connected) are kernels_dev.h's.
 // PRIO (the template parameter beside OPT): the priority-frontier mode of a forest without a goal (src/forest.h:126-147,
 // 160-181, 360-363; PrioView).  The wave's node comes from a heap of a tree (pop / pop at a drawn index), an accepted node
 // is pushed onto every heap of its tree at once, an exhausted node leaves the tree's other heaps, an expanded one goes back
@@ -216,24 +213,12 @@
         nq += (unsigned long long)R;                               // :262-267 one radiusSearch per tree
         // ---- the neighbours: exact 6-D ball of radius max(parentDistance, treeDistance) from the cells its box touches
         const double r = pdist > A.dist_tree ? pdist : A.dist_tree;
-        const double ri = (r + A.sweep_abs_eps) * (1.0 + 1e-5);
-        const float rf = sqrtf((float)(ri * ri) * 1.000001f) * 1.000001f;
-        const GridView& g = A.g;
-        const float qx = (float)qp[0], qy = (float)qp[1], qz = (float)qp[2];
-        const int lx = grid_coord(qx - rf, g.ox, g.inv_cell, g.nx), hx = grid_coord(qx + rf, g.ox, g.inv_cell, g.nx);
-        const int ly = grid_coord(qy - rf, g.oy, g.inv_cell, g.ny), hy = grid_coord(qy + rf, g.oy, g.inv_cell, g.ny);
-        const int lz = grid_coord(qz - rf, g.oz, g.inv_cell, g.nz), hz = grid_coord(qz + rf, g.oz, g.inv_cell, g.nz);
-        const int wx = hx - lx + 1, wy = hy - ly + 1, wz = hz - lz + 1;
-        const int total = wx * wy * wz;
-        auto take = [&](bool valid, const GridItem* src) {        // one candidate per lane -> the hit list in LDS
+        grid_ball_items(A.g, qp, ball_box_radius(r, A.sweep_abs_eps), lane, [&](bool valid, const GridItem* src) {   // one candidate per lane -> the hit list in LDS
           bool h = false;
           double d = 0, p6[6];
           int id = 0, tr = 0;
           if (valid) {
-            const unsigned long long* q8 = reinterpret_cast<const unsigned long long*>(src);
-            for (int k = 0; k < 6; ++k) p6[k] = __longlong_as_double((long long)sq_u64(q8 + k));
-            const unsigned long long it = sq_u64(q8 + 6);
-            id = (int)(unsigned)(it & 0xffffffffULL); tr = (int)(unsigned)(it >> 32);
+            grid_item_load(src, p6, id, tr);
             d = dist6(p6, qp);
             h = d < r;
           }
@@ -243,38 +228,7 @@
             if (at < 64) { h_id[at] = id; h_tree[at] = tr; h_d[at] = d; for (int k = 0; k < 6; ++k) h_pos[6 * at + k] = p6[k]; }
           }
           n_hit += __popcll(hm);
-        };
-        for (int c0 = 0; c0 < total; c0 += 64) {
-          const int ci = c0 + lane;
-          int cell = 0, m = 0;
-          if (ci < total) {
-            const int q1 = ci / wx, q2 = q1 / wy;
-            cell = ((lz + q2) * g.ny + (ly + q1 - q2 * wy)) * g.nx + (lx + ci - q1 * wx);
-            m = sq_i32(g.cnt + cell);
-            if (m > g.bk) m = g.bk;
-          }
-          int inc = m;
-          for (int off = 1; off < 64; off <<= 1) {
-            const int o = __shfl_up(inc, off);
-            if (lane >= off) inc += o;
-          }
-          const int tot = __shfl(inc, 63);
-          for (int base = 0; base < tot; base += 64) {
-            const int j = base + lane;
-            const int jj = j < tot ? j : tot - 1;
-            int lo = 0, hi = 63;
-            while (lo < hi) {
-              const int mid = (lo + hi) >> 1;
-              if (__shfl(inc, mid) > jj) hi = mid; else lo = mid + 1;
-            }
-            const int src_cell = __shfl(cell, lo);
-            const int slot = jj - (__shfl(inc, lo) - __shfl(m, lo));
-            take(j < tot, g.items + (size_t)src_cell * g.bk + slot);
-          }
-        }
-        int no = sq_i32(g.ovf_cnt);
-        if (no > g.ovf_cap) no = g.ovf_cap;
-        for (int base = 0; base < no; base += 64) take(base + lane < no, g.ovf + base + lane);
+        });
         if (n_hit > A.hit_cap || n_hit > 64) flt = true;
       }
       lap(4);
@@ -288,12 +242,7 @@
         const double d = have ? h_d[lane] : 0.0;
         const bool same = t == mine;
         const bool qk = have && (same ? (!force && d < pdist - SFFG_TOL) : (d < A.dist_tree - SFFG_TOL));   // :276 / :283
-        int rank = 0;
-        for (int j = 0; j < n_hit; ++j) {
-          const int tj = __shfl(t, j), idj = __shfl(id, j), qj = __shfl((int)qk, j);
-          const double dj = __shfl(d, j);
-          if (qj && (tj < t || (tj == t && (dj < d || (dj == d && idj < id))))) ++rank;
-        }
+        const int rank = nb_rank(n_hit, t, d, id, qk);
         const int n_q = __popcll(__ballot(qk));
         for (int rk = 0; rk < n_q && !reject && !flt; ++rk) {
           const unsigned long long sel = __ballot(qk && rank == rk);
@@ -320,16 +269,9 @@
             const bool fr = (sq_edge_clear_fast(A.env, cpos, np6, lane, cc, ex_smp) || sq_path_free(A.env, A.rob, rtri, stack, cand, queue, stage, cpos, np6, &s_fh, &s_ovf, lane, cc, ex_smp, flt));
             if (fr && !flt) {                                      // :288-294 border entry unless the pair has one
               const int a = s_id < node ? s_id : node, b = s_id < node ? node : s_id;
-              const unsigned long long key = ((unsigned long long)(uint32_t)a << 32) | ((unsigned long long)(uint32_t)b + 1ULL);
-              size_t h = (size_t)((key * 0x9E3779B97F4A7C15ULL) >> 17) & (size_t)f.bt_mask;
-              bool fresh = false;
-              for (int guard = 0; guard < (1 << 24); ++guard) {
-                const unsigned long long cur = sq_u64(f.bt_key + h);
-                if (cur == key) { fresh = sq_u64(f.bt_val + h) == ~0ULL; break; }
-                if (cur == 0ULL) { fresh = true; break; }
-                h = (h + 1) & (size_t)f.bt_mask;
-              }
-              if (fresh) {
+              const unsigned long long key = border_key(a, b);
+              size_t h;
+              if (border_probe<true>(f, key, h)) {
                 if (lane == 0) {
                   f.bt_key[h] = key;
                   f.bt_val[h] = c->epoch << 32;
@@ -464,12 +406,9 @@
         if (solving) {   // :369-372 the one border of a goal forest: (new node, goal), cost after choose-parent
           const int gid = f.goal_id;
           const int a = gid < idn ? gid : idn, b = gid < idn ? idn : gid;
-          const unsigned long long key = ((unsigned long long)(uint32_t)a << 32) | ((unsigned long long)(uint32_t)b + 1ULL);
-          size_t h = (size_t)((key * 0x9E3779B97F4A7C15ULL) >> 17) & (size_t)f.bt_mask;
-          for (int guard = 0; guard < (1 << 24); ++guard) {        // (the new node has no entry yet: the first free slot)
-            if (sq_u64(f.bt_key + h) == 0ULL) break;
-            h = (h + 1) & (size_t)f.bt_mask;
-          }
+          const unsigned long long key = border_key(a, b);
+          size_t h;
+          (void)border_probe<true>(f, key, h);                     // (the new node has no entry yet: the first free slot)
           if (lane == 0) {
             f.bt_key[h] = key;
             f.bt_val[h] = c->epoch << 32;
@@ -543,19 +482,8 @@
     bool conn_test = !solved && empty_frontier;
     if constexpr (GOAL) conn_test = false;   // :198 with a goal only reaching it solves
     if (conn_test) {
-      // maxConnected() == numRoots: every tree reachable from tree 0 over pairs that hold a border (R <= 64: a lane per tree)
-      unsigned long long reach = 1ULL, frontier_set = 1ULL;
-      if (R <= 64) {
-        unsigned long long row = 0ULL;   // lane a: bit b = pair (a, b) has a border
-        if (lane < R) for (int b2 = 0; b2 < R; ++b2) if (sq_u8(f.pair + (size_t)lane * R + b2)) row |= 1ULL << b2;
-        while (frontier_set) {
-          const int a = __ffsll((long long)frontier_set) - 1;
-          frontier_set &= frontier_set - 1;
-          const unsigned long long ra = __shfl(row, a) & ~reach;
-          reach |= ra; frontier_set |= ra;
-        }
-        solved = __popcll(reach) == R ? 1 : 0;
-      } else fault = SFFK_FAULT_LISTS;   // (more trees than lanes: the round engine's serial walk)
+      if (R <= 64) solved = trees_connected(f.pair, R, lane) ? 1 : 0;   // maxConnected() == numRoots
+      else fault = SFFK_FAULT_LISTS;   // (more trees than lanes: the round engine's serial walk)
     }
     const bool budget = f.node_budget > 0 && n_nodes >= f.node_budget;
     terminated = (solved || iter >= f.max_iterations || budget) ? 1 : 0;

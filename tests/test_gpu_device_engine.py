@@ -282,8 +282,8 @@ def test_saturating_forest_terminates_solved_with_closed_list_picks(S, ctx):
     assert_same_forest(fo, fg)
 
 
-def test_waves_of_one_slot_run_as_one_persistent_wavefront(S, ctx):
-    """wave = 1 - the reference's own loop order - on ONE wavefront (SFFGPU_SPEC=0: k_seq_waves runs whole outer iterations back
+def test_waves_of_one_slot_run_as_one_persistent_wavefront(S, ctx, tmp_path):
+    """wave = 1 - the reference's own loop order - on ONE wavefront (SFFGPU_SPEC=0: k_seq_waves_batch with one member runs whole outer iterations back
     to back inside one launch; the speculative kernel of round 6 is tested below and falls back to this one).  Staged runs with
     getters in between, the node budget, a forced hit-list overflow (that wave is finished on the host engine) - against the
     oracle's sequential loop - and the round engine at wave 1 gives the same forest.  (The saturating forest - closed-list
@@ -303,6 +303,15 @@ def test_waves_of_one_slot_run_as_one_persistent_wavefront(S, ctx):
     assert fr.stats()["graph_launches"] > 0                  # ... the round engine does: the knob chose the path)
     assert fr.fingerprint() == fp
     fr.close()
+    # the per-wave trace (SFFGPU_SEQ_TRACE=<file>): the kernel finds its buffer through the arguments it reads from device
+    # memory - a row of 8 int32 per wave, column 5 = the nodes after the wave
+    trace = tmp_path / "seq_trace.bin"
+    _, ft = make(S, ctx, "dense3d_coarse", 1, 6000, seed=2, SFFGPU_SPEC=0, SFFGPU_SEQ_TRACE=str(trace))
+    ft.run()
+    rows = np.fromfile(str(trace), dtype=np.int32)
+    assert rows.size == 8 * ft.stats()["waves"]
+    assert rows.reshape(-1, 8)[-1, 5] == ft.stats()["n_nodes"]
+    ft.close()
     # staged, with a node budget
     fo, fg = make(S, ctx, "triang", 1, 10 ** 7, seed=5, budget=3000, SFFGPU_SPEC=0)
     fo.run()
@@ -353,7 +362,7 @@ def test_waves_of_one_slot_speculated_over_many_wavefronts(S, ctx, name, iters, 
              sg["spec_evaluated"], sg["spec_evaluated"] / sg["spec_committed"]))
     fp = fg.fingerprint()
     fg.close()
-    _, f1 = make(S, ctx, name, 1, iters, seed=seed, optimize=optimize, SFFGPU_SPEC=0)     # one wavefront (k_seq_waves)
+    _, f1 = make(S, ctx, name, 1, iters, seed=seed, optimize=optimize, SFFGPU_SPEC=0)     # one wavefront (k_seq_waves_batch)
     f1.run()
     assert f1.fingerprint() == fp and f1.stats()["spec_steps"] == 0
     f1.close()
@@ -405,7 +414,7 @@ def test_speculated_waves_staged_budget_faults_and_parity_mode(S, ctx):
         sg = fg.stats()
         assert_same_forest(fo, fg)
         if knob & 7 == 0:
-            assert 0 < sg["spec_steps"] <= 41 and sg["spec_committed"] < fo.stats()["iterations"]      # the rest: k_seq_waves
+            assert 0 < sg["spec_steps"] <= 41 and sg["spec_committed"] < fo.stats()["iterations"]      # the rest: k_seq_waves_batch
         elif sg["spec_committed"] < fo.stats()["iterations"]:
             mid_wave += 1
             assert sg["host_fallback_waves"] == 1
