@@ -11,10 +11,12 @@
 //   k_commit      wide (64 samples per workgroup): the in-order commit of one round.  A sample whose neighbour walk
 //                 reaches an EARLIER sample of the same round polls that sample's state; accepted samples get their
 //                 node ids from the lower workgroups' published counts (slot order); border events are de-duplicated
-//                 "first in slot order wins" through a stamped hash table; the round's last workgroup writes the
+//                 "first in slot order wins" through a stamped hash table; SFF*: the round's last workgroup writes the
 //                 control block.  Workgroups wait for lower ones only (see the kernel)
 //   k_append_sample  wide: accepted samples -> node store, neighbour grid, frontier; the slots that were not accepted
-//                 form the next round's active list AND draw that round's samples in the same launch
+//                 form the next round's active list AND draw that round's samples in the same launch; plain SFF: its
+//                 last workgroup writes the control block for the commit, the others derive what they need of it
+//                 from the block as the commit found it (commit_next.h)
 //   k_wave_end_wide  256 slots per workgroup: exhausted slots move their node to the closed list (first occurrence in slot
 //                 order) and mark their frontier position; termination tests (src/forest.h:184-201)
 //   k_frontier_compact  wide: order-preserving removal of the marked positions (the reference erases them one by
@@ -28,6 +30,7 @@
 #include "kernels.h"
 #include "sff_geom.h"
 #include "kernels_dev.h"
+#include "commit_next.h"
 
 namespace sffk {
 
@@ -40,37 +43,7 @@ __device__ __forceinline__ int32_t* act_now(const DevForestView& f) { return f.c
 
 // Sizes the next round from the active list (already in place, act_cnt entries): src/forest.h:155 - i <
 // ThresholdMisses && expandResult && iter < maxIterations.  Thread 0 of the single workgroup.
-__device__ void round_begin_scalars(const DevForestView& f, DevCtrl* c) {
-  const int cnt = c->act_cnt;
-  int n = 0;
-  if (c->round < f.threshold_misses && cnt > 0 && c->iter < f.max_iterations && !c->solved) {
-    const int left = f.max_iterations - c->iter;
-    n = cnt < left ? cnt : left;
-  }
-  c->n_act = n;
-  if (n > 0) {
-    // the arrays a round can grow: one node / frontier entry / border per sample at most
-    if (c->n_nodes + n > f.node_cap - 8 || c->n_borders + n > f.border_cap) {
-      c->fault = SFFK_FAULT_CAPACITY;
-      c->halt = 1;
-      c->n_act = 0;
-    } else if ((unsigned long long)(c->n_borders + n) * 2ULL > f.bt_mask + 1ULL) {
-      c->fault = SFFK_FAULT_BORDER_TABLE;
-      c->halt = 1;
-      c->n_act = 0;
-    } else {
-      c->round += 1;
-      c->iter0 = c->iter;
-      c->iter += n;
-      c->N0 = c->n_nodes;
-      c->words_base = c->cursor;
-      c->cursor += (unsigned long long)f.words_per * (unsigned long long)n;
-      c->rounds += 1;
-      c->round_nodes += (unsigned long long)(c->n_nodes + n);
-      c->round_queries += (unsigned long long)n;
-    }
-  }
-}
+__device__ void round_begin_scalars(const DevForestView& f, DevCtrl* c) { round_begin_next(f, c); }   // (commit_next.h)
 
 // ------------------------------------------------------------------ wave begin
 // Wide: one slot per thread; the workgroup that gets through last writes the control block (the picks themselves are
@@ -219,7 +192,8 @@ __device__ __forceinline__ size_t border_slot(const DevForestView& f, unsigned l
 //   - a border key belongs to the first event in slot order: an event knows its fate once the lower workgroups (and its
 //     own) have posted their stamps (atomicMin on the table entry) - later stamps can only be larger.
 // So a workgroup waits for lower ones only, and workgroups start in index order: the lowest unfinished one never waits.
-// The LAST workgroup of the round adds everything up and writes the control block.
+// SFF*: the LAST workgroup of the round adds everything up and writes the control block.  Plain SFF: nothing in this
+// kernel consumes the totals - the append launch behind it adds them up and writes the block (commit_finalize).
 // Published words are (launch sequence number << 32 | value): nothing is cleared between launches.
 // (a fault raised in a walk has reached the L2 before its workgroup publishes a word: the round's last workgroup reads the
 // flag as soon as it has every lower workgroup's count)
@@ -234,6 +208,23 @@ __device__ __forceinline__ size_t border_slot(const DevForestView& f, unsigned l
 #define KC_CNT 6      // 6 counters of the walks + [12] dependent samples
 #define KC_DEP 12
 #define KC_EVN 13     // border events (before the first-in-slot-order rule)
+// Plain SFF: what k_commit leaves for the finalize block of the append launch (commit_finalize) besides the workgroups'
+// lines - the sampling workgroups of that launch reset the query clock's shards and the round's scratch block for the
+// NEXT round, so the finalize block cannot read either itself.  Words 2.. of the first shard's line (DevForestView::qclk_sh:
+// a shard uses words 0 and 1 of its 16), written by workgroup 0 and by the round's last workgroup.
+#define KH_QBEG 2     // the query kernel's clock bracket, folded over the 64 shards
+#define KH_QEND 3
+#define KH_WORK 4     // the round's work items (ResolveArgs::round_ctrl[2])
+#define KH_PASSES 5   // polls of the last workgroup's walk phase
+#define KH_PHASE 6    // its three phase clocks, words 6..8 (SFFGPU_PROFILE): walks, lower workgroups' counts, borders
+#define KH_MATE_EV 9  // border events whose neighbour was accepted in the same round (SFFGPU_PROFILE; the finalize block takes
+                      // the count into DevCtrl::prof[4] and puts the word back to zero)
+#define KH_NB0 10     // the border count before the round: the block's n_borders word is rewritten with the exact count by
+                      // the append launch's own border_finalize, unordered with that launch's other workgroups' loads
+// ... and the counters the workgroups of the append launch count themselves in with once their first batch of loads is in:
+// word KH_READY of EVERY shard's line, workgroup b into shard b % 64 (atomics on ONE address retire one after the other -
+// some 400 of them were 3 us of the finalize block's wait; 64 addresses on lines of their own are not)
+#define KH_READY 15
 
 __device__ __forceinline__ unsigned long long kc_load(const unsigned long long* p) {
   return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
@@ -273,6 +264,21 @@ __device__ __forceinline__ void kc_block_sum8(unsigned long long* v, unsigned lo
     for (int q = from; q < 8; ++q) if (v[q]) atomicAdd(&slots[q], v[q]);
   __syncthreads();
   for (int q = from; q < 8; ++q) v[q] = slots[q];
+}
+
+// the round's counters into the control block: tot = the six counters of the walks + [6] dependent samples
+__device__ __forceinline__ void commit_counters(DevCtrl& K, const unsigned long long* tot, int work_items, bool have_q,
+                                                unsigned long long q_beg, unsigned long long q_end) {
+  K.collide_calls += tot[0];
+  K.path_free_calls += tot[1];
+  K.nn_queries += tot[2];
+  K.poses_executed += tot[3];
+  K.segments_executed += tot[4];
+  K.samples_executed += tot[5];
+  K.n_unsettled += (int)tot[6];
+  K.work_items += (unsigned long long)work_items;
+  if (have_q) { K.q_t0 = q_beg; K.q_t1 = q_end; }
+  if (K.q_t1 > K.q_t0) { K.q_ticks += K.q_t1 - K.q_t0; K.q_launches += 1ULL; }
 }
 
 __global__ __launch_bounds__(1024) void k_commit(ResolveArgs A, int n_bound) {
@@ -325,11 +331,29 @@ __global__ __launch_bounds__(1024) void k_commit(ResolveArgs A, int n_bound) {
   unsigned long long* trace = (f.kc_trace && (int)c->rounds == f.kc_trace_round && threadIdx.x == 0) ? f.kc_trace + 8 * (size_t)b : nullptr;
 #define KC_TRACE(k) do { if (trace) trace[k] = wall_clock64(); } while (0)
   KC_TRACE(0);
+  // SFF*: the round's last workgroup adds everything up and writes the control block (step 5: the star stage between this
+  // launch and the append reads it).  Plain SFF: the finalize block of the append launch does (commit_finalize) - this
+  // kernel ends when its slowest workgroup has walked and published, and leaves the block as it found it.
+  const bool tail = last && A.star;
   int work_items = 0;
-  if (last) {   // (the control block does not change before this workgroup rewrites it: requested now, used at the end)
+  if (tail) {   // (the control block does not change before this workgroup rewrites it: requested now, used at the end)
     for (int w = threadIdx.x; w < (int)(sizeof(DevCtrl) / 4); w += 1024)
       reinterpret_cast<int32_t*>(&K)[w] = reinterpret_cast<const int32_t*>(c)[w];
     work_items = A.round_ctrl[2];
+  }
+  if (!A.star && b == 0 && threadIdx.x < 64) {
+    // the query kernel's clock bracket (every workgroup of it reported into one of 64 shards) and the round's work items,
+    // for the finalize block: the launch it runs in resets both for the next round (KH_*).  Workgroup 0 waits for nobody.
+    unsigned long long q_end = f.qclk_sh[threadIdx.x * 16], q_beg = f.qclk_sh[threadIdx.x * 16 + 1];
+    const int wi = A.round_ctrl[2];
+    for (int off = 32; off > 0; off >>= 1) {
+      const unsigned long long e2 = __shfl_xor(q_end, off), b2 = __shfl_xor(q_beg, off);
+      q_end = e2 > q_end ? e2 : q_end; q_beg = b2 < q_beg ? b2 : q_beg;
+    }
+    if (threadIdx.x == 0) {
+      f.qclk_sh[KH_QBEG] = q_beg; f.qclk_sh[KH_QEND] = q_end; f.qclk_sh[KH_WORK] = (unsigned long long)wi;
+      f.qclk_sh[KH_NB0] = (unsigned long long)(unsigned)nb0;
+    }
   }
 
   // ---- 1. every sample's walk, as far as the states of the earlier samples allow
@@ -535,10 +559,10 @@ __global__ __launch_bounds__(1024) void k_commit(ResolveArgs A, int n_bound) {
   // ---- 3. node ids: N0 + accepted samples before, in slot order
   unsigned long long part = 0;
   if ((int)threadIdx.x < b) part = kc_wait(f.wg_pub + (size_t)threadIdx.x * SFFK_PUB_WORDS + KC_ACC, seq, f.commit_seq + 6);
-  // (the last workgroup: the lower workgroups' counters were published before their counts - requested now, looked at
+  // (SFF*, the last workgroup: the lower workgroups' counters were published before their counts - requested now, looked at
   // when the control block is written)
   unsigned long long early[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-  if (last && (int)threadIdx.x < b)   // (behind the count: published before it)
+  if (tail && (int)threadIdx.x < b)   // (behind the count: published before it)
     for (int q = 0; q < 8; ++q) early[q] = kc_load(f.wg_pub + (size_t)threadIdx.x * SFFK_PUB_WORDS + KC_CNT + q);
   const int acc_pref = (int)kc_block_sum(part, &s_sum);
   // The round's fault flag (a bounded list that overflowed, the goal reached: raised in a workgroup's WALKS, before it
@@ -547,7 +571,7 @@ __global__ __launch_bounds__(1024) void k_commit(ResolveArgs A, int n_bound) {
   // be asked for there: a round trip on the round's critical path).  A wait that gives up (never: KC_SPIN_LIMIT) raises
   // commit_seq[6] instead, which ends the run at the wave's end (SFFK_FAULT_INTERNAL).
   int fault_seen = 0;
-  if (last && threadIdx.x == 1023) fault_seen = __hip_atomic_load(A.fault_pending, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  if (tail && threadIdx.x == 1023) fault_seen = __hip_atomic_load(A.fault_pending, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
   if (threadIdx.x == 0) {
     f.acc_pref[b] = acc_pref;
     kc_publish(pub + KC_PREF, seq, (unsigned)acc_pref);
@@ -558,6 +582,10 @@ __global__ __launch_bounds__(1024) void k_commit(ResolveArgs A, int n_bound) {
   KC_TRACE(4);
   // ---- 4. border events (a free edge to a neighbour of another tree, :288-294), first in slot order wins
   int n_own = 0, ev_pref = 0;
+  if (f.profile && !A.star && threadIdx.x < 64) {   // (how often the one consumer of the id prefix in this kernel runs)
+    const unsigned long long wm = __ballot(is_ev && !stamped);
+    if (threadIdx.x == 0 && wm) atomicAdd(&f.qclk_sh[KH_MATE_EV], (unsigned long long)__popcll(wm));
+  }
   if (we != 0ULL || last) {
     if (is_ev && !stamped) {                 // (a round-mate neighbour was accepted: its new id)
       const int raw = A.rec_nb[(size_t)e_i * A.nbcap + s_dk[threadIdx.x]];
@@ -642,9 +670,16 @@ __global__ __launch_bounds__(1024) void k_commit(ResolveArgs A, int n_bound) {
     }
   }
   KC_TRACE(7);
-  if (!last) return;
-  // ---- 5. the last workgroup of the round: totals, the control block (the next round's active list = the slots of this
-  // round that were not accepted, then the slots the iteration cap kept out of it: k_append writes it)
+  if (last && !A.star && threadIdx.x == 0) {   // (for the profile line: written with the control block, by commit_finalize)
+    f.qclk_sh[KH_PASSES] = (unsigned long long)passes;
+    if (clk) {
+      tk[3] = wall_clock64();
+      for (int q = 0; q < 3; ++q) f.qclk_sh[KH_PHASE + q] = tk[q + 1] - tk[q];
+    }
+  }
+  if (!tail) return;
+  // ---- 5. SFF*, the last workgroup of the round: totals, the control block (the next round's active list = the slots of
+  // this round that were not accepted, then the slots the iteration cap kept out of it: k_append writes it)
   if (clk) tk[3] = wall_clock64();
   // the query kernel's clock bracket: every workgroup of it reported into one of 64 shards (DevForestView::qclk_sh)
   unsigned long long q_end = 0ULL, q_beg = ~0ULL;
@@ -666,65 +701,28 @@ __global__ __launch_bounds__(1024) void k_commit(ResolveArgs A, int n_bound) {
   for (int q = 0; q < 7; ++q) tot[q] += s_c6[q];
   tot[7] += (unsigned long long)__popcll(we);
   // (deferred: every event counted - an upper bound until the append launch has entered the ones that own their key)
-  const int n_acc = acc_pref + __popcll(wa), n_ev = defer ? (int)tot[7] : ev_pref + n_own, n_dep = (int)tot[6];
+  const int n_acc = acc_pref + __popcll(wa), n_ev = defer ? (int)tot[7] : ev_pref + n_own;
   const bool faulted = s_ev_total != 0;
-  auto roll_back = [&](DevCtrl* k) {
-    // a bounded device list overflowed somewhere in this round: nothing is committed, the bookkeeping of the round's
-    // begin is rolled back and the host redoes the round on its unbounded path
-    k->fault = SFFK_FAULT_LISTS;
-    k->halt = 1;
-    k->round -= 1;
-    k->iter = k->iter0;
-    k->cursor = k->words_base;
-    k->rounds -= 1;
-    k->round_nodes -= (unsigned long long)(k->N0 + n);
-    k->round_queries -= (unsigned long long)n;
-    k->n_act = 0;
-    k->app_n = 0;
-  };
   if (A.star && !faulted) {
     // SFF*: the star stage may still fault after this kernel has committed the round's bookkeeping (a member edge's
     // candidate list, the fixed point's launch budget): the control block as a rolled-back round leaves it, for k_star_apply
     for (int w = threadIdx.x; w < (int)(sizeof(DevCtrl) / 4); w += 1024)
       reinterpret_cast<int32_t*>(A.S.backup)[w] = reinterpret_cast<const int32_t*>(&K)[w];
     __syncthreads();
-    if (threadIdx.x == 0) roll_back(A.S.backup);
+    if (threadIdx.x == 0) commit_roll_back(A.S.backup);
   }
   if (threadIdx.x == 0) {
     if (faulted) {
-      roll_back(&K);
+      commit_roll_back(&K);
       *A.fault_pending = 0;
       if (A.star) { A.S.hdr[0] = 0; A.S.hdr[1] = 1; A.S.hdr[2] = 0; A.S.hdr[4] = 0; }
     } else {
-      const int fn0 = K.frontier_n, act_cnt = K.act_cnt, act_sel = K.act_sel;
-      K.collide_calls += tot[0];
-      K.path_free_calls += tot[1];
-      K.nn_queries += tot[2];
-      K.poses_executed += tot[3];
-      K.segments_executed += tot[4];
-      K.samples_executed += tot[5];
-      K.work_items += (unsigned long long)work_items;
-      if (f.qclk_sh) { K.q_t0 = q_beg; K.q_t1 = q_end; }
-      if (K.q_t1 > K.q_t0) { K.q_ticks += K.q_t1 - K.q_t0; K.q_launches += 1ULL; }
-      K.app_n = n;                  // k_append applies this commit
-      K.app_N0 = N0;
-      K.app_fn0 = fn0;
-      K.app_act_sel = act_sel;
-      K.app_act_cnt = act_cnt;
-      K.iter0_app = K.iter0;
-      K.n_nodes = N0 + n_acc;
-      K.frontier_n = f.prio.n_heaps ? fn0 : fn0 + n_acc;
-      K.n_borders = nb0 + n_ev;
-      K.app_nb0 = nb0;
-      K.n_unsettled += n_dep;
-      K.epoch += 1ULL;
+      commit_counters(K, tot, work_items, f.qclk_sh != nullptr, q_beg, q_end);
+      commit_next_round(f, &K, n_acc, n_ev, false);   // (commit_next.h)
       if (A.star) {
         K.nn_queries += (unsigned long long)n_acc;       // one knnSearch per accepted sample (src/forest.h:317)
         A.S.hdr[0] = n_acc; A.S.hdr[1] = 0; A.S.hdr[2] = n_ev; A.S.hdr[3] = nb0; A.S.hdr[4] = 0;
       }
-      K.act_sel = act_sel ^ 1;
-      K.act_cnt = (n - n_acc) + (act_cnt - n);
-      round_begin_scalars(f, &K);
       if (clk) {
         tk[4] = wall_clock64();
         for (int q = 0; q < 4; ++q) K.prof[q] += tk[q + 1] - tk[q];
@@ -745,25 +743,134 @@ __global__ __launch_bounds__(1024) void k_commit(ResolveArgs A, int n_bound) {
 // One slot's share of the append.  Returns the slot's index in the NEXT round's active list (-1: none - accepted, or
 // nothing was committed) and the slot itself.
 // part: 0 = everything, 1 = only the accepted sample's node (k_append_sample: the next round's list and the claims of a
-// wave that is over are written by its sampling workgroups, append_list_one).
-__device__ __forceinline__ void append_ord_store(const ResolveArgs& A, int ord_at, int next) {
-  if (ord_at >= 0) (A.f.ctrl->app_act_sel ? A.f.ord.lst[0] : A.f.ord.lst[1])[ord_at] = next;
+// wave that is over are written by its sampling workgroups, append_list_request / append_list_store).
+//
+// What a workgroup of the append launch knows of the commit it applies and of the round behind it.  SFF*: k_commit has
+// written the control block, the fields are read from it (app_ctl_block).  Plain SFF: the block is still the one the
+// commit found, the finalize block of this very launch rewrites it (commit_finalize) - every other workgroup derives the
+// fields from the old block and the round's totals (hand_request / hand_derive) and never reads the block again.
+struct AppCtl {
+  int32_t n, N0, fn0, act_sel, act_cnt, iter0, nb0;   // the committed round (n = 0: nothing was committed)
+  int32_t new_cnt;                                     // entries of the next round's active list
+  int32_t wave_over;                                   // no next round: the slots still on the list are exhausted
+  int32_t ord_valid;
+  unsigned seq;                                        // the commit's launch number, its epoch (border_finalize)
+  unsigned long long epoch;
+};
+__device__ __forceinline__ AppCtl app_ctl_block(const DevForestView& f) {
+  const DevCtrl* c = f.ctrl;
+  AppCtl a;
+  a.n = c->app_n; a.N0 = c->app_N0; a.fn0 = c->app_fn0; a.act_sel = c->app_act_sel; a.act_cnt = c->app_act_cnt;
+  a.iter0 = c->iter0_app; a.nb0 = c->app_nb0; a.new_cnt = c->act_cnt;
+  a.wave_over = (c->n_act == 0 && !c->halt && c->in_wave && !c->use_closed) ? 1 : 0;
+  a.ord_valid = c->ord_valid;
+  a.seq = (unsigned)f.commit_seq[0];
+  a.epoch = c->epoch;
+  return a;
 }
-__device__ __forceinline__ int append_one(const ResolveArgs& A, int i, int& slot_out, int& ord_at, int part = 0) {
-  ord_at = -1;
+// The first batch of loads of a workgroup of the append launch, plain SFF: the control block as the commit found it (the
+// fields commit_next_round reads, and what the sampler needs beside them), the round's fault flag, the commit's launch
+// number and - LINES: the workgroups that need the round's totals - ONE workgroup line of k_commit per thread, accepted
+// samples and border events, summed over the workgroup in hand_derive.  All of it is final: k_commit has ended, and
+// the finalize block stores nothing before every other workgroup of the launch has counted itself in (KH_READY) behind
+// this batch.
+struct HandIn {
+  CommitRegs k;
+  int32_t in_wave, use_closed, ord_valid, n_slots, act_identity, fault, seq0;
+  unsigned long long acc, evn;
+};
+template <bool LINES> __device__ __forceinline__ HandIn hand_request(const ResolveArgs& A, int n_lines) {
   const DevForestView& f = A.f;
   const DevCtrl* c = f.ctrl;
-  const int n = c->app_n;
+  HandIn h{};
+  if (LINES) {
+    const unsigned long long* pp = f.wg_pub + (size_t)((int)threadIdx.x < n_lines ? threadIdx.x : 0) * SFFK_PUB_WORDS;
+    h.acc = pp[KC_ACC]; h.evn = pp[KC_EVN];
+  }
+  h.k = commit_regs_load(c, (int32_t)f.qclk_sh[KH_NB0]);   // (commit_next.h: the one list of the fields; n_borders from KH_NB0)
+  h.in_wave = c->in_wave; h.use_closed = c->use_closed; h.ord_valid = c->ord_valid; h.n_slots = c->n_slots;
+  h.act_identity = c->act_identity;
+  h.fault = A.fault_pending[0];
+  h.seq0 = f.commit_seq[0];
+  return h;
+}
+__device__ __forceinline__ void hand_join(HandIn& h) {
+  join_v(h.k.n_act, h.k.halt, h.k.iter, h.k.round, h.k.solved, h.k.N0, h.k.iter0, h.k.n_borders, h.k.frontier_n, h.k.act_sel,
+         h.k.act_cnt, h.k.cursor, h.k.epoch, h.in_wave, h.use_closed, h.ord_valid, h.n_slots, h.act_identity, h.fault, h.seq0,
+         h.acc, h.evn);
+}
+// A round that did not run (halted, empty) leaves everything as it is: n = 0, nobody counts itself in, the finalize
+// block stores nothing.
+__device__ __forceinline__ bool hand_ran(const HandIn& h) { return !(h.k.halt || h.k.n_act == 0); }
+// A workgroup of the launch counts itself in behind its first batch (hand_join and a barrier: every wavefront's loads)
+__device__ __forceinline__ void hand_count_in(const ResolveArgs& A) {
+  atomicAdd(&A.f.qclk_sh[(blockIdx.x & 63) * 16 + KH_READY], 1ULL);
+}
+__device__ __forceinline__ AppCtl hand_app_ctl(const HandIn& h, const CommitRegs& k) {
+  AppCtl a{};
+  a.n = k.app_n; a.N0 = k.app_N0; a.fn0 = k.app_fn0; a.act_sel = k.app_act_sel; a.act_cnt = k.app_act_cnt;
+  a.iter0 = k.iter0_app; a.nb0 = k.app_nb0; a.new_cnt = k.act_cnt;
+  a.wave_over = (k.n_act == 0 && !k.halt && h.in_wave && !h.use_closed) ? 1 : 0;
+  a.ord_valid = h.ord_valid;
+  a.seq = (unsigned)h.seq0 + 1u;
+  a.epoch = k.epoch;
+  return a;
+}
+// What the append has to apply, from the old block alone (commit_applied: no totals) - all that the workgroups which create
+// the nodes or enter the border events need.  new_cnt and wave_over are NOT the next round's.  Every thread of the
+// workgroup calls it behind hand_join (one barrier inside: every wavefront's first batch has returned).
+__device__ __forceinline__ AppCtl hand_applied(const ResolveArgs& A, const HandIn& h) {
+  if (!hand_ran(h)) { AppCtl a{}; a.ord_valid = h.ord_valid; return a; }
+  __syncthreads();
+  if (threadIdx.x == 0) hand_count_in(A);
+  CommitRegs k = h.k;
+  commit_applied(&k, h.fault != 0);
+  return hand_app_ctl(h, k);
+}
+// The round's totals over the workgroup lines - a word counts when it carries this commit's launch number, the lines
+// above the round's size are stale - one trip through LDS; h.k then becomes the control block the finalize block writes
+// (commit_next_round).  Every thread of the workgroup calls it behind hand_join (one barrier inside, behind which the
+// workgroup counts itself in).
+__device__ __forceinline__ AppCtl hand_derive(const ResolveArgs& A, HandIn& h, int n_lines, unsigned long long* s_part) {
+  const DevForestView& f = A.f;
+  if (!hand_ran(h)) { AppCtl a{}; a.ord_valid = h.ord_valid; return a; }
+  const unsigned seq = (unsigned)h.seq0 + 1u;
+  auto line = [&](unsigned long long acc, unsigned long long evn) -> unsigned long long {
+    return ((unsigned)(acc >> 32) == seq ? (unsigned long long)(unsigned)acc : 0ULL) |
+           ((unsigned)(evn >> 32) == seq ? (unsigned long long)(unsigned)evn << 32 : 0ULL);
+  };
+  unsigned long long v = (int)threadIdx.x < n_lines ? line(h.acc, h.evn) : 0ULL;   // (accepted | events << 32)
+  for (int t = threadIdx.x + 256; t < n_lines; t += 256) {   // (waves above 16 384 slots)
+    const unsigned long long* pp = f.wg_pub + (size_t)t * SFFK_PUB_WORDS;
+    v += line(pp[KC_ACC], pp[KC_EVN]);
+  }
+  // (a wavefront's share: 64 threads x 4 lines x 64 samples at most - 16 bits each, one register through the shuffles)
+  unsigned pk = (unsigned)v | ((unsigned)(v >> 32) << 16);
+  for (int off = 32; off > 0; off >>= 1) pk += __shfl_xor(pk, off);
+  if ((threadIdx.x & 63) == 0) s_part[threadIdx.x >> 6] = (unsigned long long)(pk & 0xffffu) | ((unsigned long long)(pk >> 16) << 32);
+  __syncthreads();
+  if (threadIdx.x == 0) hand_count_in(A);
+  v = s_part[0] + s_part[1] + s_part[2] + s_part[3];
+  commit_next_round(f, &h.k, (int)(unsigned)v, (int)(v >> 32), h.fault != 0);
+  return hand_app_ctl(h, h.k);
+}
+__device__ __forceinline__ void append_ord_store(const ResolveArgs& A, const AppCtl& C, int ord_at, int next) {
+  if (ord_at >= 0) (C.act_sel ? A.f.ord.lst[0] : A.f.ord.lst[1])[ord_at] = next;
+}
+__device__ __forceinline__ int append_one(const ResolveArgs& A, const AppCtl& C, int i, int& slot_out, int& ord_at, int part = 0) {
+  ord_at = -1;
+  const DevForestView& f = A.f;
+  const int n = C.n;
   slot_out = -1;
   if (n <= 0) return -1;
-  const int act_cnt = c->app_act_cnt;
-  const int32_t* act_old = c->app_act_sel ? f.act_slot2 : f.act_slot;
-  int32_t* act_new = c->app_act_sel ? f.act_slot : f.act_slot2;
+  const int act_cnt = C.act_cnt;
+  const int32_t* act_old = C.act_sel ? f.act_slot2 : f.act_slot;
+  int32_t* act_new = C.act_sel ? f.act_slot : f.act_slot2;
   // the wave is over with this commit (no next round): the slots still on the list are exhausted - each claims its node
   // (atomicMin of its place in the list: a node held by several slots moves to the closed list once, at its first slot,
   // src/forest.h:160-178) and parks it for k_wave_end_wide, which would otherwise post the claims itself and meet at a counter first
-  const bool wave_over = c->n_act == 0 && !c->halt && c->in_wave && !c->use_closed;
-  const bool ord_on = f.ord.hist && c->ord_valid;
+  const bool wave_over = C.wave_over != 0;
+  const bool ord_on = f.ord.hist && C.ord_valid;
   auto claim = [&](int e, int slot) {
     const int nd = f.slot_node[slot];
     atomicMin(&f.claim[nd], e);
@@ -774,7 +881,7 @@ __device__ __forceinline__ int append_one(const ResolveArgs& A, int i, int& slot
     // the slots the iteration cap kept out of the committed round stay on the list, behind the still-failing ones
     // (the cap has been reached: they never draw again)
     if (i < act_cnt && part != 1) {
-      const int e = (c->act_cnt - (act_cnt - n)) + (i - n), slot = act_old[i];
+      const int e = (C.new_cnt - (act_cnt - n)) + (i - n), slot = act_old[i];
       act_new[e] = slot;
       if (wave_over) claim(e, slot);
     }
@@ -788,11 +895,11 @@ __device__ __forceinline__ int append_one(const ResolveArgs& A, int i, int& slot
     // accepted it has nothing else to do), so that the sampling half's chain stays as short as it was
     auto ord_append = [&](int slot) {
       const int sub = f.ord.slot_pos[slot] >> 6;
-      const bool first = c->app_act_sel != 0;   // (the buffer that is NOT the committed round's)
+      const bool first = C.act_sel != 0;   // (the buffer that is NOT the committed round's)
       ord_at = sub * 64 + atomicAdd(&(first ? f.ord.cnt[0] : f.ord.cnt[1])[sub * SFFK_ORD_CNT_STRIDE], 1);
     };
     if (part == 1) {
-      if (ord_on) { ord_append(act_old[i]); append_ord_store(A, ord_at, i - rank); }
+      if (ord_on) { ord_append(act_old[i]); append_ord_store(A, C, ord_at, i - rank); }
       return -1;
     }
     slot_out = act_old[i];
@@ -802,8 +909,8 @@ __device__ __forceinline__ int append_one(const ResolveArgs& A, int i, int& slot
     return i - rank;
   }
   if (A.star) return -1;   // SFF*: k_star_apply has made the accepted samples nodes
-  const int N0 = c->app_N0, fn0 = c->app_fn0;
-  int32_t* const frontier = frontier_now(f);
+  const int N0 = C.N0, fn0 = C.fn0;
+  int32_t* const frontier = frontier_now(f);   // (front_sel: no commit changes it)
   const int id = N0 + rank;
   const int ex = A.parent[i];
   const double* p = A.newpos + 6 * (size_t)i;
@@ -821,7 +928,7 @@ __device__ __forceinline__ int append_one(const ResolveArgs& A, int i, int& slot
   f.parent[o] = ex;                                  // src/forest.h:353
   f.d_closest[o] = pd;
   f.d_root[o] = pd + f.d_root[ex];
-  f.iter[o] = (uint32_t)(c->iter0_app + i + 1);
+  f.iter[o] = (uint32_t)(C.iter0 + i + 1);
   f.nflag[o] = f.prio.n_heaps ? 0 : 2;
   if (!f.prio.n_heaps) frontier[fn0 + rank] = id;    // :365 (priority mode: the tree's heaps, at the wave's end - k_prio_end)
   grid_put(A.g, it);                                 // flannIndex->addPoints, :367
@@ -831,19 +938,20 @@ __device__ __forceinline__ int append_one(const ResolveArgs& A, int i, int& slot
 // beside the append's own workgroups: an event owns its key when its stamp is the table entry's minimum (every stamp of
 // the round is in the table - k_commit has ended), its place in the list is border count before the round + the owned
 // events of the LOWER workgroups (published like k_commit's words, polled; a workgroup waits for lower ones only) + its
-// rank in the workgroup.  The round's last workgroup writes the exact border count over k_commit's upper bound.
-__device__ void border_finalize(const ResolveArgs& A, int b) {
+// rank in the workgroup.  The round's last workgroup writes the exact border count over the commit's upper bound (the one
+// word of the control block the finalize block leaves alone, with claims_done and the sampler's clock reset).
+__device__ void border_finalize(const ResolveArgs& A, const AppCtl& C, int b) {
   __shared__ unsigned long long s_bsum;
   __shared__ int s_bown;
   const DevForestView& f = A.f;
   DevCtrl* c = f.ctrl;
-  const int n = c->app_n;
+  const int n = C.n;
   if (n <= 0 || A.star) return;
   const int nwg = (n + 63) >> 6;
   if (b >= nwg) return;
-  const unsigned seq = (unsigned)f.commit_seq[0];                 // (the commit's launch number)
-  const unsigned long long stamp_hi = c->epoch << 32;             // (the commit's epoch: incremented when it committed)
-  const int Tb = f.temp_base, nb0 = c->app_nb0;
+  const unsigned seq = C.seq;                                     // (the commit's launch number)
+  const unsigned long long stamp_hi = C.epoch << 32;              // (the commit's epoch: incremented when it committed)
+  const int Tb = f.temp_base, nb0 = C.nb0;
   const unsigned long long we = f.w_ev[b];
   unsigned long long* pub = f.wg_pub + (size_t)b * SFFK_PUB_WORDS;
   const int tid = threadIdx.x;
@@ -899,11 +1007,128 @@ __device__ void border_finalize(const ResolveArgs& A, int b) {
   }
   if (last && tid == 0) c->n_borders = nb0 + ev_pref + n_own;
 }
-__global__ __launch_bounds__(256) void k_append(ResolveArgs A, int append_blocks) {
-  if ((int)blockIdx.x >= append_blocks) { border_finalize(A, (int)blockIdx.x - append_blocks); return; }
+// Plain SFF: the finalize block - the append launch's workgroup with the highest index writes the control block for the
+// commit that k_commit has settled: totals over the workgroups' lines (final since k_commit ended: one batch of loads,
+// nothing is polled), the query clock bracket and the work items (KH_*), the counters, commit_next_round (a faulted
+// round is rolled back), the profile clocks, the commit's launch number.  The other workgroups of the launch read the
+// OLD block in their first batch and derive the same values (hand_derive): nothing is stored - control block, fault
+// flag, launch number - before all `others` of them have counted themselves in (64 counters, KH_READY: the first
+// wavefront polls one each).  Workgroups start in index order, so this one
+// waits for started ones only; the wait is bounded like kc_wait (then commit_seq[6]: the run ends at the wave's end).
+// Words other workgroups of the launch write are left alone: the exact border count (border_finalize), claims_done
+// (the wave's last append) and - sampler = the launch also draws the next round - the reset of q_t0 / q_t1.  n_borders
+// is thereby the one word of the block that is rewritten while the launch's workgroups take their first loads: nobody
+// reads it there (the copy below is overwritten), the count before the round comes from KH_NB0.
+__device__ void commit_finalize(const ResolveArgs& A, int others, bool sampler) {
+  __shared__ DevCtrl K;
+  __shared__ unsigned long long s_stash[9];   // KH_QBEG .. KH_NB0
+  __shared__ unsigned s_red[9][4];
+  __shared__ int s_fault;
+  const DevForestView& f = A.f;
+  DevCtrl* c = f.ctrl;
+  const int tid = threadIdx.x;
+  const unsigned long long t0 = f.profile ? wall_clock64() : 0ULL;
+  // one batch: the control block, what k_commit left beside the lines, the fault flag, the lines themselves
+  for (int w = tid; w < (int)(sizeof(DevCtrl) / 4); w += 256)
+    reinterpret_cast<int32_t*>(&K)[w] = reinterpret_cast<const int32_t*>(c)[w];
+  if (tid >= 128 && tid < 128 + 9) s_stash[tid - 128] = f.qclk_sh[KH_QBEG + tid - 128];
+  if (tid == 255) s_fault = A.fault_pending[0];
+  const int halt = c->halt, n = c->n_act;
+  if (halt || n == 0) return;   // (no round ran: the block stays as it is, and nobody counts itself in)
+  const unsigned seq = (unsigned)f.commit_seq[0] + 1u;
+  const int nwg = (n + 63) >> 6;
+  // (a workgroup publishes its count last: its stamp vouches for the line.  32-bit values and partial sums - a round's
+  // totals are far below 2^32 - because the launch shares its register budget with the sampler)
+  unsigned tot[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};   // 6 counters, dependent samples, border events, accepted samples
+  bool stale = false;
+  for (int t = tid; t < nwg; t += 256) {
+    const unsigned long long* pp = f.wg_pub + (size_t)t * SFFK_PUB_WORDS;
+    const unsigned* lo = reinterpret_cast<const unsigned*>(pp + KC_CNT);
+    unsigned v[8];
+    for (int q = 0; q < 8; ++q) v[q] = lo[2 * q];
+    const unsigned long long va = pp[KC_ACC];
+    stale = stale || (unsigned)(va >> 32) != seq;
+    for (int q = 0; q < 8; ++q) tot[q] += v[q];
+    tot[8] += (unsigned)va;
+  }
+  if (stale) atomicOr(f.commit_seq + 6, 1);   // (never: a workgroup of the round whose words are not this commit's)
+  for (int q = 0; q < 9; ++q) {
+    for (int off = 32; off > 0; off >>= 1) tot[q] += __shfl_xor(tot[q], off);
+    if ((tid & 63) == 0) s_red[q][tid >> 6] = tot[q];
+  }
+  __syncthreads();
+  if (tid == 0) {
+    unsigned long long sum[9];
+    for (int q = 0; q < 9; ++q) sum[q] = (unsigned long long)s_red[q][0] + s_red[q][1] + s_red[q][2] + s_red[q][3];
+    const bool faulted = s_fault != 0;
+    // (the block's own n_borders word may already hold this launch's exact count, border_finalize: the count before the
+    // round is the one k_commit left)
+    K.n_borders = (int32_t)s_stash[KH_NB0 - KH_QBEG];
+    if (!faulted) commit_counters(K, sum, (int)s_stash[KH_WORK - KH_QBEG], true, s_stash[0], s_stash[KH_QEND - KH_QBEG]);
+    // (every event counted: an upper bound until this launch's border_finalize has entered the ones that own their key)
+    commit_next_round(f, &K, (int)sum[8], (int)sum[7], faulted);
+  }
+  if (tid < 64) {   // (the first wavefront: workgroups b = tid, tid + 64, .. below this one count into shard tid)
+    unsigned long long* rdy = f.qclk_sh + tid * 16 + KH_READY;
+    const unsigned long long want = (unsigned long long)((others - tid + 63) / 64);
+    bool in = false;
+    for (int spin = 0; spin < KC_SPIN_LIMIT; ++spin) {
+      in = __hip_atomic_load(rdy, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) >= want;
+      if (__all(in)) break;
+      __builtin_amdgcn_s_sleep(1);
+    }
+    // (a wait that gave up - never - still puts the counters back to zero: a workgroup that counts itself in afterwards
+    // leaves its 1 behind for the next launch, whose finalize block could then store too early.  Harmless only because
+    // commit_seq[6] ends the run at this wave's end, SFFK_FAULT_INTERNAL)
+    if (!in) atomicOr(f.commit_seq + 6, 1);
+    __hip_atomic_store(rdy, 0ULL, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    // (the round's count of same-round border events is taken, or - a faulted round - dropped: k_commit has ended)
+    if (tid == 0 && f.profile) f.qclk_sh[KH_MATE_EV] = 0ULL;
+  }
+  if (tid == 0) {
+    const bool faulted = s_fault != 0;
+    const unsigned long long passes = s_stash[KH_PASSES - KH_QBEG];
+    if (!faulted) {
+      if (f.profile) {   // (the last k_commit workgroup's phases; "control block" = this workgroup, the wait included)
+        for (int q = 0; q < 3; ++q) K.prof[q] += s_stash[KH_PHASE - KH_QBEG + q];
+        K.prof[3] += wall_clock64() - t0;
+        K.prof[4] += s_stash[KH_MATE_EV - KH_QBEG];
+      }
+      K.prof[5] += passes;
+      K.prof[6] += 1ULL;
+      if (passes > K.prof[7]) K.prof[7] = passes;
+    } else {
+      *A.fault_pending = 0;
+    }
+    f.commit_seq[0] = (int32_t)seq;
+  }
+  __syncthreads();
+  constexpr int W_NB = (int)(offsetof(DevCtrl, n_borders) / 4), W_CD = (int)(offsetof(DevCtrl, claims_done) / 4),
+                W_Q0 = (int)(offsetof(DevCtrl, q_t0) / 4), W_Q1 = (int)(offsetof(DevCtrl, q_ticks) / 4);
+  for (int w = tid; w < (int)(sizeof(DevCtrl) / 4); w += 256) {
+    if (w == W_NB || w == W_CD || (sampler && w >= W_Q0 && w < W_Q1)) continue;
+    reinterpret_cast<int32_t*>(c)[w] = reinterpret_cast<const int32_t*>(&K)[w];
+  }
+}
+__global__ __launch_bounds__(256) void k_append(ResolveArgs A, int append_blocks, int n_lines) {
+  __shared__ unsigned long long s_hand[4];
+  if (!A.star && blockIdx.x == gridDim.x - 1) { commit_finalize(A, (int)gridDim.x - 1, false); return; }
+  const bool border = (int)blockIdx.x >= append_blocks;
+  AppCtl C;
+  if (A.star) C = app_ctl_block(A.f);
+  else if (border) {
+    HandIn h = hand_request<false>(A, n_lines);
+    hand_join(h);
+    C = hand_applied(A, h);
+  } else {   // (the next round's list length, the claims of a wave that is over: the totals)
+    HandIn h = hand_request<true>(A, n_lines);
+    hand_join(h);
+    C = hand_derive(A, h, n_lines, s_hand);
+  }
+  if (border) { border_finalize(A, C, (int)blockIdx.x - append_blocks); return; }
   int slot, ord_at;
-  const int next = append_one(A, blockIdx.x * 256 + threadIdx.x, slot, ord_at);
-  append_ord_store(A, ord_at, next);
+  const int next = append_one(A, C, blockIdx.x * 256 + threadIdx.x, slot, ord_at);
+  append_ord_store(A, C, ord_at, next);
 }
 // The sampling workgroups' share of the commit: the next round's active list (+ the claims of a wave that is over), and
 // which sample of the next round - if any - thread i draws, from which node.  Everything the thread index addresses is
@@ -913,42 +1138,66 @@ __global__ __launch_bounds__(256) void k_append(ResolveArgs A, int append_blocks
 // the slot itself is only stored (the next list) and, when the wave is over, claimed.  A.parent is the committed round's
 // list, the sampler's parent_out the other one of the two: reading the one while the other is written is no race.
 // bound = the launch bound (the lists hold that many entries whatever the round's size): clamped indices keep the
-// threads behind it harmless.  Returns the sample's index in the next round (-1: none); K = the sampler's control fields.
-__device__ __forceinline__ int append_list_one(const ResolveArgs& A, int i, int bound, int& par, SampleCtl& K) {
+// threads behind it harmless.  L.next = the sample's index in the next round (-1: none); K = the sampler's control fields.
+// Plain SFF: the control-block fields are the ones the commit found.  Which slot draws which sample needs the
+// committed round's size and list only (commit_applied); the next round's size, list length and "the wave is over" come
+// from the round's totals (hand_derive, in the kernel) - the stores and the sample's second batch wait for them.
+struct ListOne { int i, n, act_cnt, app_sel, new_cnt, slot, ex, next; bool wave_over; };
+__device__ __forceinline__ void append_list_request(const ResolveArgs& A, int i, int bound, int n_lines, HandIn& h, SampleCtl& K,
+                                                    ListOne& L) {
   const DevForestView& f = A.f;
   const DevCtrl* c = f.ctrl;   // (the sampler's control block too)
   const int ic = i < bound ? i : bound - 1;
+  if (!A.star) h = hand_request<true>(A, n_lines);
   unsigned long long w = f.w_acc[ic >> 6];
   int pref = f.acc_pref[ic >> 6];
   int s0 = f.act_slot[ic], s1 = f.act_slot2[ic];
   int ex = A.parent[ic];
-  K = sample_ctl(c);
-  int n = c->app_n, act_cnt = c->app_act_cnt, app_sel = c->app_act_sel, new_cnt = c->act_cnt;
-  int in_wave = c->in_wave, use_closed = c->use_closed;
-  join_ctl_v(K);
-  join_v(n, act_cnt, app_sel, new_cnt, in_wave, use_closed, w, pref, s0, s1, ex);
-  const bool wave_over = K.n == 0 && !K.halt && in_wave && !use_closed;
-  par = 0;
-  if (n <= 0) return -1;
-  const int slot = app_sel ? s1 : s0;
-  int32_t* act_new = app_sel ? f.act_slot : f.act_slot2;
-  if (wave_over && i == 0) f.ctrl->claims_done = 1;
+  L.i = i; L.n = 0; L.act_cnt = 0; L.app_sel = 0; L.new_cnt = 0; L.wave_over = false;
+  if (A.star) {
+    K = sample_ctl(c);
+    int n = c->app_n, act_cnt = c->app_act_cnt, app_sel = c->app_act_sel, new_cnt = c->act_cnt;
+    int in_wave = c->in_wave, use_closed = c->use_closed;
+    join_ctl_v(K);
+    join_v(n, act_cnt, app_sel, new_cnt, in_wave, use_closed, w, pref, s0, s1, ex);
+    L.n = n; L.act_cnt = act_cnt; L.app_sel = app_sel; L.new_cnt = new_cnt;
+    L.wave_over = K.n == 0 && !K.halt && in_wave && !use_closed;
+  } else {
+    hand_join(h);
+    join_v(w, pref, s0, s1, ex);
+    K = SampleCtl{};
+    K.words_base = h.k.cursor;   // (a next round's words start where the cursor stands)
+    if (hand_ran(h)) {
+      CommitRegs k = h.k;
+      commit_applied(&k, h.fault != 0);
+      L.n = k.app_n; L.act_cnt = k.app_act_cnt; L.app_sel = k.app_act_sel;
+    }
+  }
+  L.slot = L.app_sel ? s1 : s0;
+  L.ex = ex;
+  // not accepted: the slot tries again - the accepted samples before it leave the list (accepted: the node-creating
+  // workgroups, SFF*: k_star_apply, have it)
+  L.next = (i < L.n && !((w >> (i & 63)) & 1ULL)) ? i - (pref + __popcll(w & ((1ULL << (i & 63)) - 1ULL))) : -1;
+}
+__device__ __forceinline__ void append_list_store(const ResolveArgs& A, const ListOne& L) {
+  const DevForestView& f = A.f;
+  const int i = L.i, n = L.n;
+  if (n <= 0) return;
+  int32_t* act_new = L.app_sel ? f.act_slot : f.act_slot2;
+  if (L.wave_over && i == 0) f.ctrl->claims_done = 1;
   if (i >= n) {
     // the slots the iteration cap kept out of the committed round stay on the list, behind the still-failing ones
     // (the cap has been reached: they never draw again; they drew nothing in the committed round either - no parent entry)
-    if (i < act_cnt) {
-      const int e = (new_cnt - (act_cnt - n)) + (i - n);
-      act_new[e] = slot;
-      if (wave_over) { const int nd = f.slot_node[slot]; atomicMin(&f.claim[nd], e); f.ulist[e] = nd; }
+    if (i < L.act_cnt) {
+      const int e = (L.new_cnt - (L.act_cnt - n)) + (i - n);
+      act_new[e] = L.slot;
+      if (L.wave_over) { const int nd = f.slot_node[L.slot]; atomicMin(&f.claim[nd], e); f.ulist[e] = nd; }
     }
-    return -1;
+    return;
   }
-  if ((w >> (i & 63)) & 1ULL) return -1;   // accepted: the node-creating workgroups (SFF*: k_star_apply) have it
-  const int next = i - (pref + __popcll(w & ((1ULL << (i & 63)) - 1ULL)));   // (the accepted samples before it leave the list)
-  par = ex;
-  act_new[next] = slot;                  // not accepted: the slot tries again
-  if (wave_over) { atomicMin(&f.claim[ex], next); f.ulist[next] = ex; }
-  return next;
+  if (L.next < 0) return;
+  act_new[L.next] = L.slot;
+  if (L.wave_over) { atomicMin(&f.claim[L.ex], L.next); f.ulist[L.next] = L.ex; }
 }
 // k_append + the NEXT round's k_sample_steer in one launch: a slot that was not accepted draws its next sample right
 // away (its place in the next round's list is its old place minus the accepted samples before it; the round's size,
@@ -958,23 +1207,40 @@ __device__ __forceinline__ int append_list_one(const ResolveArgs& A, int i, int 
 // between two sets of these arrays (A = the committed round's, P = the next round's).
 // The first half of the workgroups creates the accepted samples' nodes, the second half writes the list and samples: a
 // wavefront that had to do both would run the two chains of dependent loads one after the other.
-__global__ __launch_bounds__(256) void k_append_sample(ResolveArgs A, SampleLaunch P, int append_blocks) {
-  if ((int)blockIdx.x >= 2 * append_blocks) { border_finalize(A, (int)blockIdx.x - 2 * append_blocks); return; }
+__global__ __launch_bounds__(256) void k_append_sample(ResolveArgs A, SampleLaunch P, int append_blocks, int n_lines) {
+  __shared__ unsigned long long s_hand[4];
+  if (!A.star && blockIdx.x == gridDim.x - 1) { commit_finalize(A, (int)gridDim.x - 1, true); return; }
   const int nb = append_blocks;
-  const bool sampler = (int)blockIdx.x >= nb;
-  const int tid = ((int)blockIdx.x - (sampler ? nb : 0)) * 256 + threadIdx.x;
+  const bool sampler = (int)blockIdx.x >= nb && (int)blockIdx.x < 2 * nb;
   if (!sampler) {
+    AppCtl C;
+    if (A.star) C = app_ctl_block(A.f);
+    else {   // (node ids, frontier places, iteration stamps, border entries: nothing of the round's totals)
+      HandIn h = hand_request<false>(A, n_lines);
+      hand_join(h);
+      C = hand_applied(A, h);
+    }
+    if ((int)blockIdx.x >= 2 * nb) { border_finalize(A, C, (int)blockIdx.x - 2 * nb); return; }
     int slot, ord_at;
-    (void)append_one(A, tid, slot, ord_at, 1);
+    (void)append_one(A, C, blockIdx.x * 256 + threadIdx.x, slot, ord_at, 1);
     return;
   }
-  int par;
+  const int tid = ((int)blockIdx.x - nb) * 256 + threadIdx.x;
+  HandIn h{};
   SampleCtl K;
-  const int next = append_list_one(A, tid, P.n, par, K);
+  ListOne L;
+  append_list_request(A, tid, P.n, n_lines, h, K, L);
+  if (!A.star) {
+    const AppCtl C = hand_derive(A, h, n_lines, s_hand);
+    K.n = h.k.n_act; K.halt = h.k.halt; K.act_sel = h.k.act_sel; K.round = h.k.round;
+    K.ord_valid = h.ord_valid; K.n_slots = h.n_slots; K.act_identity = h.act_identity;
+    L.new_cnt = C.new_cnt; L.wave_over = C.wave_over != 0;
+  }
+  append_list_store(A, L);
   if (K.halt) return;
-  const bool valid = next >= 0 && next < K.n;
-  const SampleIn S = sample_fetch(valid ? next : 0, valid ? par : 0, K, P);
-  sample_finish(tid, valid, next, par, S, -1, K, P);
+  const bool valid = L.next >= 0 && L.next < K.n;
+  const SampleIn S = sample_fetch(valid ? L.next : 0, valid ? L.ex : 0, K, P);
+  sample_finish(tid, valid, L.next, valid ? L.ex : 0, S, -1, K, P);
 }
 
 // the control block at the end of a wave: closed list / frontier sizes, termination (src/forest.h:184-201); one thread
@@ -1268,10 +1534,11 @@ void launch_commit(hipStream_t s, const ResolveArgs& a, int n_bound, const StarL
   if (n_bound <= 0) return;
   hipLaunchKernelGGL(k_commit, dim3((n_bound + 63) / 64), dim3(1024), 0, s, a, n_bound);
   if (a.star && star) launch_star_stage(s, a, n_bound, *star);
-  // (plain SFF: + one workgroup per 64 samples that enters the round's border events, border_finalize)
-  const int ab = (n_bound + 255) / 256, fb = a.star ? 0 : (n_bound + 63) / 64;
-  if (next) hipLaunchKernelGGL(k_append_sample, dim3(2 * ab + fb), dim3(256), 0, s, a, *next, ab);
-  else hipLaunchKernelGGL(k_append, dim3(ab + fb), dim3(256), 0, s, a, ab);
+  // (plain SFF: + one workgroup per 64 samples that enters the round's border events, border_finalize, + the finalize
+  // block that writes the control block, commit_finalize: the highest index)
+  const int ab = (n_bound + 255) / 256, lines = (n_bound + 63) / 64, fb = a.star ? 0 : lines + 1;
+  if (next) hipLaunchKernelGGL(k_append_sample, dim3(2 * ab + fb), dim3(256), 0, s, a, *next, ab, lines);
+  else hipLaunchKernelGGL(k_append, dim3(ab + fb), dim3(256), 0, s, a, ab, lines);
 }
 void launch_wave_end(hipStream_t s, const DevForestView& f, const int32_t* grid_ovf, const int32_t* tgrid_ovf,
                      unsigned long long* star_acc) {

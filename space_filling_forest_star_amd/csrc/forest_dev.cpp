@@ -1752,11 +1752,15 @@ void Forest::run_device(int max_waves) {
                 used, names[k], sv.front(), sv[sv.size() / 2], sv.back(), v.front(), v.back());
       }
     }
-    // (the LAST workgroup's clock: what the others do is over by then)
+    // (the LAST workgroup's clock: what the others do is over by then.  Plain SFF: the control block is written by the
+    // append launch's finalize block, beside that launch's other work - its clock, the wait for the other workgroups' first
+    // loads included; SFF*: by k_commit's last workgroup, as part of that kernel's critical path)
     fprintf(stderr, "[sffgpu k_commit us/commit, last workgroup] walks + waits for earlier samples %.1f (%.2f polls, max %llu) "
-            "lower workgroups' counts %.1f borders %.1f control block %.1f | dependent/round %.0f\n", k.prof[0] / r / 100.0, k.prof[5] / r,
-            (unsigned long long)k.prof[7], k.prof[1] / r / 100.0, k.prof[2] / r / 100.0, k.prof[3] / r / 100.0,
-            (double)k.n_unsettled / r);
+            "lower workgroups' counts %.1f borders %.1f | control block (%s) %.1f | dependent/round %.0f | "
+            "border events with a neighbour accepted in the same round %llu\n", k.prof[0] / r / 100.0, k.prof[5] / r,
+            (unsigned long long)k.prof[7], k.prof[1] / r / 100.0, k.prof[2] / r / 100.0,
+            cfg.optimize ? "in k_commit" : "finalize block of the append launch", k.prof[3] / r / 100.0,
+            (double)k.n_unsettled / r, (unsigned long long)k.prof[4]);
 #ifdef SFFK_CI_TRACE
     {
       std::vector<unsigned long long> tr(4096 * 8);

@@ -148,7 +148,8 @@ struct RobotView {
 };
 
 // ---- device-resident forest (devforest.hip): the round loop of SpaceForest::Solve with the in-order commit on the
-// GPU.  DevCtrl lives in HBM, is advanced by the last workgroup of k_wave_begin / k_commit and by the one-workgroup k_wave_end and is
+// GPU.  DevCtrl lives in HBM, is advanced by the last workgroup of k_wave_begin, by the commit (plain SFF: the finalize
+// block of the append launch, commit_next.h; SFF*: k_commit's last workgroup) and by k_wave_end and is
 // copied to the host once per wave.  Every round kernel reads the number of samples from it (the host launches
 // grids sized for the wave), and returns at once when `halt` is set (solver terminated, or a fault the host has
 // to handle: a device list overflowed and the round must be redone on the host path).
@@ -175,8 +176,9 @@ struct DevCtrl {
   unsigned long long epoch;         // commit counter (border dedup stamps)
   unsigned long long work_items;    // (edge, chunk) items of all rounds
   // k_commit phase clocks (wall_clock64 ticks of 10 ns, thread 0 of the round's LAST workgroup, SFFGPU_PROFILE only):
-  // walks + waits for earlier samples, lower workgroups' counts (ids), borders, totals + control block;
-  // [5] = polls of the walk phase, [6] = commits, [7] = most polls
+  // walks + waits for earlier samples, lower workgroups' counts (ids), borders, totals + control block (plain SFF: the
+  // clock of the append launch's finalize block, which writes the block); [4] = plain SFF: border events whose neighbour
+  // was accepted in the same round; [5] = polls of the walk phase, [6] = commits, [7] = most polls
   unsigned long long prof[8];
   // device-clock bracket of the neighbour-query kernel of the current round (first wave in .. last wave out, 100 MHz
   // wall_clock64 ticks) and its sum over all committed rounds: the duration rocprofv3 reports, without the ~3 us a
@@ -519,13 +521,16 @@ struct DevForestView {
   int32_t* ustate32;           // per sample: (seq << 2 | state), state 1 rejected / 2 accepted / 3 rejected + border event
   unsigned long long* wg_pub;  // SFFK_PUB_WORDS words per workgroup of 64 samples (one 128-byte line), see k_commit
   int32_t* commit_seq;         // [0] = launches that reached their end so far; [1] workgroups of k_wave_begin that are through, [2] one of them met a redraw;
-                               // [3] = k_wave_end_wide launches that ended a wave, [4] its workgroups that are through
+                               // [3] = k_wave_end_wide launches that ended a wave, [4] its workgroups that are through,
+                               // [6] = a wait gave up (never)
   unsigned long long* kc_trace; int32_t kc_trace_round;   // SFFGPU_KC_TRACE=<round>: 8 clock reads per workgroup of that round's k_commit
   DevCtrl* host_status;        // SFFK_STATUS_RING control blocks in pinned host memory (device-visible); null = the host copies
   // Device-clock bracket of the neighbour-query kernel, by EVERY workgroup (round 6; round 5 sampled every 16th one and so
   // could miss the last workgroup out): 64 shards of {latest end, earliest start} on lines of their own (16 words apart) -
   // thread 0 of workgroup b adds its two clock reads to shard b % 64 with atomics that return nothing; the sampling launch
-  // in front resets them, k_commit's last workgroup folds them into DevCtrl::q_t0 / q_t1
+  // in front resets them, the commit folds them into DevCtrl::q_t0 / q_t1.  Never null on the device engine: words 2.. of
+  // the first shard's line carry what k_commit leaves for the append launch's finalize block, word 15 of every line counts that
+  // launch's workgroups in (devforest.hip: KH_*)
   unsigned long long* qclk_sh;
   int32_t profile;             // SFFGPU_PROFILE: the single-workgroup kernels read their phase clocks (a clock read is a scalar
                                // memory round trip: a dozen of them is microseconds)
