@@ -117,4 +117,45 @@ template <class C> SFF_HD void commit_next_round(const DevForestView& f, C* k, i
   round_begin_next(f, k);
 }
 
+// ---- node ids, plain SFF: the accepted samples before each 64-sample group, from the workgroup lines k_commit leaves.
+// A line's KC_ACC word is (launch number << 32 | accepted samples of the workgroup); it counts when it carries the
+// commit's launch number `seq`.  The lines above the round's size are thereby out: their workgroups leave before they
+// publish, the words still carry an earlier launch's number.
+SFF_HD unsigned commit_line_count(unsigned long long word, unsigned seq) {
+  return (unsigned)(word >> 32) == seq ? (unsigned)word : 0u;
+}
+// The prefix has two levels, the ones a workgroup of the append launch computes it in (hand_lines, devforest.hip): the
+// lines in chunks of 64 - one wavefront's lines, scanned across its lanes there - and the chunks' totals, part[k] (low half:
+// accepted samples of chunk k; the device keeps the chunk's border events in the high half).  SFFK_DEV_MAX_GROUPS lines
+// at most, so 16 chunks.
+#define SFFK_LINE_CHUNKS (SFFK_DEV_MAX_GROUPS / 64)
+// accepted samples of every chunk below group g's.  part[0..3] are always there (chunks without lines hold 0): a wave of
+// up to 16 384 slots reads them in one go and selects, only larger waves walk on (a loop of dependent LDS reads on the
+// device).
+SFF_HD int commit_prefix_base(const unsigned long long* part, int g) {
+  const int c = g >> 6;
+  const int p0 = (int)(unsigned)part[0], p1 = (int)(unsigned)part[1], p2 = (int)(unsigned)part[2], p3 = (int)(unsigned)part[3];
+  int base = (c > 0 ? p0 : 0) + (c > 1 ? p1 : 0) + (c > 2 ? p2 : 0) + (c > 3 ? p3 : 0);
+  for (int k = 4; k < c; ++k) base += (int)(unsigned)part[k];
+  return base;
+}
+// pref[g] = accepted samples of the groups below g (a sample's node id = N0 + pref[i >> 6] + its rank in its word);
+// returns the round's accepted samples, -1 for more lines than a wave can have.  acc = the KC_ACC word of line 0,
+// `stride` words from one line to the next.  tests/commit_prefix_harness.cpp holds it against a plain running sum.
+SFF_HD int commit_line_prefix(const unsigned long long* acc, int stride, int n_lines, unsigned seq, int32_t* pref) {
+  if (n_lines < 0 || n_lines > SFFK_DEV_MAX_GROUPS) return -1;
+  unsigned long long part[SFFK_LINE_CHUNKS] = {};
+  const int chunks = (n_lines + 63) >> 6;
+  for (int k = 0; k < chunks; ++k) {
+    unsigned run = 0;                                   // (the wavefront's scan: exclusive within the chunk)
+    for (int g = k * 64; g < n_lines && g < k * 64 + 64; ++g) {
+      pref[g] = (int32_t)run;
+      run += commit_line_count(acc[(size_t)g * (size_t)stride], seq);
+    }
+    part[k] = run;
+  }
+  for (int g = 0; g < n_lines; ++g) pref[g] += commit_prefix_base(part, g);
+  return commit_prefix_base(part, chunks * 64);
+}
+
 }  // namespace sffk

@@ -10,9 +10,10 @@
 //                 exact incl. the rejection redraw: src/forest.h:136-151), then the first round's active list
 //   k_commit      wide (64 samples per workgroup): the in-order commit of one round.  A sample whose neighbour walk
 //                 reaches an EARLIER sample of the same round polls that sample's state; accepted samples get their
-//                 node ids from the lower workgroups' published counts (slot order); border events are de-duplicated
-//                 "first in slot order wins" through a stamped hash table; SFF*: the round's last workgroup writes the
-//                 control block.  Workgroups wait for lower ones only (see the kernel)
+//                 node ids from the lower workgroups' published counts (slot order; plain SFF: added up by the append
+//                 launch, not here); border events are de-duplicated "first in slot order wins" through a stamped hash
+//                 table; SFF*: the round's last workgroup writes the control block.  Workgroups wait for lower ones
+//                 only (see the kernel)
 //   k_append_sample  wide: accepted samples -> node store, neighbour grid, frontier; the slots that were not accepted
 //                 form the next round's active list AND draw that round's samples in the same launch; plain SFF: its
 //                 last workgroup writes the control block for the commit, the others derive what they need of it
@@ -188,7 +189,8 @@ __device__ __forceinline__ size_t border_slot(const DevForestView& f, unsigned l
 // parent edge, lane l the l-th neighbour).  Everything that needs the slot order only ever looks BACKWARDS in it:
 //   - a sample whose walk (src/forest.h:262-300) reaches a sample of the same round waits for that sample's state
 //     (ustate32, polled; the earlier sample sits in this or in a lower workgroup);
-//   - node ids / border list positions are prefixes over the LOWER workgroups' published counts;
+//   - node ids / border list positions are prefixes over the LOWER workgroups' published counts (plain SFF: the append
+//     launch adds them up - here only a workgroup with a border event whose neighbour is of this very round does);
 //   - a border key belongs to the first event in slot order: an event knows its fate once the lower workgroups (and its
 //     own) have posted their stamps (atomicMin on the table entry) - later stamps can only be larger.
 // So a workgroup waits for lower ones only, and workgroups start in index order: the lowest unfinished one never waits.
@@ -200,7 +202,7 @@ __device__ __forceinline__ size_t border_slot(const DevForestView& f, unsigned l
 #define KC_FAULT_SETTLE() asm volatile("s_waitcnt vmcnt(0)" ::: "memory")
 #define KC_SPIN_LIMIT (1 << 20)   // polls before a wait gives up (then: fault, the host redoes the round) - never reached
 #define KC_ACC 0      // accepted samples of the workgroup
-#define KC_PREF 1     // accepted samples of all lower workgroups
+#define KC_PREF 1     // accepted samples of all lower workgroups (SFF* only: plain SFF publishes no prefix)
 #define KC_WLO 2      // accepted word, low / high half
 #define KC_WHI 3
 #define KC_POSTED 4   // its border stamps are in the table
@@ -217,8 +219,9 @@ __device__ __forceinline__ size_t border_slot(const DevForestView& f, unsigned l
 #define KH_WORK 4     // the round's work items (ResolveArgs::round_ctrl[2])
 #define KH_PASSES 5   // polls of the last workgroup's walk phase
 #define KH_PHASE 6    // its three phase clocks, words 6..8 (SFFGPU_PROFILE): walks, lower workgroups' counts, borders
-#define KH_MATE_EV 9  // border events whose neighbour was accepted in the same round (SFFGPU_PROFILE; the finalize block takes
-                      // the count into DevCtrl::prof[4] and puts the word back to zero)
+#define KH_MATE_EV 9  // border events whose neighbour was accepted in the same round | those with the neighbour in a lower
+                      // workgroup << 32 (SFFGPU_PROFILE; the finalize block adds the word to DevCtrl::prof[4] and puts it
+                      // back to zero)
 #define KH_NB0 10     // the border count before the round: the block's n_borders word is rewritten with the exact count by
                       // the append launch's own border_finalize, unordered with that launch's other workgroups' loads
 // ... and the counters the workgroups of the append launch count themselves in with once their first batch of loads is in:
@@ -281,13 +284,15 @@ __device__ __forceinline__ void commit_counters(DevCtrl& K, const unsigned long 
   if (K.q_t1 > K.q_t0) { K.q_ticks += K.q_t1 - K.q_t0; K.q_launches += 1ULL; }
 }
 
-__global__ __launch_bounds__(1024) void k_commit(ResolveArgs A, int n_bound) {
+template <bool STAR> __global__ __launch_bounds__(1024) void k_commit(ResolveArgs A, int n_bound) {
   __shared__ int s_state[64], s_dk[64], s_dep[64];
   __shared__ unsigned long long s_cnt[64][6];
   __shared__ unsigned long long s_sum;
   __shared__ unsigned long long s_wa, s_we, s_c6[7];
   __shared__ int s_ev_total;
   __shared__ unsigned long long s_tot[8];
+  __shared__ unsigned long long s_wm;   // plain SFF: the workgroup's events whose neighbour is a round-mate, and the
+  __shared__ int s_bj[64];              // neighbours' workgroups (step 4)
   __shared__ DevCtrl K;
   const DevForestView& f = A.f;
   DevCtrl* c = f.ctrl;
@@ -311,7 +316,7 @@ __global__ __launch_bounds__(1024) void k_commit(ResolveArgs A, int n_bound) {
   if (halt || n == 0) {
     if (b == 0 && threadIdx.x == 0) {
       c->app_n = 0;
-      if (A.star) { A.S.hdr[0] = 0; A.S.hdr[1] = 1; A.S.hdr[2] = 0; A.S.hdr[4] = 0; }   // (no star stage unless a round commits)
+      if (STAR) { A.S.hdr[0] = 0; A.S.hdr[1] = 1; A.S.hdr[2] = 0; A.S.hdr[4] = 0; }   // (no star stage unless a round commits)
     }
     return;
   }
@@ -334,14 +339,14 @@ __global__ __launch_bounds__(1024) void k_commit(ResolveArgs A, int n_bound) {
   // SFF*: the round's last workgroup adds everything up and writes the control block (step 5: the star stage between this
   // launch and the append reads it).  Plain SFF: the finalize block of the append launch does (commit_finalize) - this
   // kernel ends when its slowest workgroup has walked and published, and leaves the block as it found it.
-  const bool tail = last && A.star;
+  const bool tail = last && STAR;
   int work_items = 0;
   if (tail) {   // (the control block does not change before this workgroup rewrites it: requested now, used at the end)
     for (int w = threadIdx.x; w < (int)(sizeof(DevCtrl) / 4); w += 1024)
       reinterpret_cast<int32_t*>(&K)[w] = reinterpret_cast<const int32_t*>(c)[w];
     work_items = A.round_ctrl[2];
   }
-  if (!A.star && b == 0 && threadIdx.x < 64) {
+  if (!STAR && b == 0 && threadIdx.x < 64) {
     // the query kernel's clock bracket (every workgroup of it reported into one of 64 shards) and the round's work items,
     // for the finalize block: the launch it runs in resets both for the next round (KH_*).  Workgroup 0 waits for nobody.
     unsigned long long q_end = f.qclk_sh[threadIdx.x * 16], q_beg = f.qclk_sh[threadIdx.x * 16 + 1];
@@ -523,7 +528,9 @@ __global__ __launch_bounds__(1024) void k_commit(ResolveArgs A, int n_bound) {
   // append launch that follows (k_border_finalize) - by then every stamp is in the table, and the two rounds of "wait
   // for every lower workgroup" (stamps posted, owned counts) leave this kernel's critical path.  SFF* needs the entries
   // in its passes: there they are settled here.
-  const bool defer = !A.star;
+  // (the SFF* instance reads the launch's flag here as the kernel did before it had two instances: with the constant the
+  // compiler gives that instance 89 vector registers instead of 87, profiles/commit_prefix_codegen.md)
+  const bool defer = STAR ? !A.star : true;
   // ---- 2b. border events (a free edge to a neighbour of another tree, :288-294) whose neighbour is a STORE node need
   // nothing of the other workgroups: their stamps go out now, and a workgroup none of whose events waits for a
   // round-mate's id says "posted" before it collects the lower workgroups' counts - the higher workgroups then find the
@@ -556,45 +563,80 @@ __global__ __launch_bounds__(1024) void k_commit(ResolveArgs A, int n_bound) {
       posted = true;
     }
   }
-  // ---- 3. node ids: N0 + accepted samples before, in slot order
-  unsigned long long part = 0;
-  if ((int)threadIdx.x < b) part = kc_wait(f.wg_pub + (size_t)threadIdx.x * SFFK_PUB_WORDS + KC_ACC, seq, f.commit_seq + 6);
-  // (SFF*, the last workgroup: the lower workgroups' counters were published before their counts - requested now, looked at
-  // when the control block is written)
+  // ---- 3. node ids: N0 + accepted samples before, in slot order.  SFF* only: the star stage reads acc_pref, KC_PREF and
+  // the list of the accepted samples.  Plain SFF: nothing on the round's chain needs the prefix - the append launch derives
+  // it from the workgroups' lines, which are final there (hand_lines) - so a workgroup is done behind its words and its
+  // store-node stamps, unless one of its events has a neighbour of this very round (step 4).
+  int acc_pref = 0;
   unsigned long long early[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-  if (tail && (int)threadIdx.x < b)   // (behind the count: published before it)
-    for (int q = 0; q < 8; ++q) early[q] = kc_load(f.wg_pub + (size_t)threadIdx.x * SFFK_PUB_WORDS + KC_CNT + q);
-  const int acc_pref = (int)kc_block_sum(part, &s_sum);
-  // The round's fault flag (a bounded list that overflowed, the goal reached: raised in a workgroup's WALKS, before it
-  // publishes anything) is final once every lower workgroup's count is in - the block sum's barriers are behind all the
-  // waits, and behind this workgroup's own walks: asked for now, looked at when the control block is written (it used to
-  // be asked for there: a round trip on the round's critical path).  A wait that gives up (never: KC_SPIN_LIMIT) raises
-  // commit_seq[6] instead, which ends the run at the wave's end (SFFK_FAULT_INTERNAL).
   int fault_seen = 0;
-  if (tail && threadIdx.x == 1023) fault_seen = __hip_atomic_load(A.fault_pending, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-  if (threadIdx.x == 0) {
-    f.acc_pref[b] = acc_pref;
-    kc_publish(pub + KC_PREF, seq, (unsigned)acc_pref);
+  if constexpr (STAR) {
+    unsigned long long part = 0;
+    if ((int)threadIdx.x < b) part = kc_wait(f.wg_pub + (size_t)threadIdx.x * SFFK_PUB_WORDS + KC_ACC, seq, f.commit_seq + 6);
+    // (the last workgroup: the lower workgroups' counters were published before their counts - requested now, looked at
+    // when the control block is written)
+    if (tail && (int)threadIdx.x < b)   // (behind the count: published before it)
+      for (int q = 0; q < 8; ++q) early[q] = kc_load(f.wg_pub + (size_t)threadIdx.x * SFFK_PUB_WORDS + KC_CNT + q);
+    acc_pref = (int)kc_block_sum(part, &s_sum);
+    // The round's fault flag (a bounded list that overflowed, the goal reached: raised in a workgroup's WALKS, before it
+    // publishes anything) is final once every lower workgroup's count is in - the block sum's barriers are behind all the
+    // waits, and behind this workgroup's own walks: asked for now, looked at when the control block is written (it used to
+    // be asked for there: a round trip on the round's critical path).  A wait that gives up (never: KC_SPIN_LIMIT) raises
+    // commit_seq[6] instead, which ends the run at the wave's end (SFFK_FAULT_INTERNAL).
+    if (tail && threadIdx.x == 1023) fault_seen = __hip_atomic_load(A.fault_pending, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    if (threadIdx.x == 0) {
+      f.acc_pref[b] = acc_pref;
+      kc_publish(pub + KC_PREF, seq, (unsigned)acc_pref);
+    }
+    if (threadIdx.x < 64 && ((wa >> threadIdx.x) & 1ULL))   // the accepted samples as a list (rank -> sample)
+      A.S.acc_sample[acc_pref + __popcll(wa & ((1ULL << threadIdx.x) - 1ULL))] = b * 64 + (int)threadIdx.x;
   }
-  if (A.star && threadIdx.x < 64 && ((wa >> threadIdx.x) & 1ULL))   // SFF*: the accepted samples as a list (rank -> sample)
-    A.S.acc_sample[acc_pref + __popcll(wa & ((1ULL << threadIdx.x) - 1ULL))] = b * 64 + (int)threadIdx.x;
   if (clk) tk[2] = wall_clock64();
   KC_TRACE(4);
   // ---- 4. border events (a free edge to a neighbour of another tree, :288-294), first in slot order wins
   int n_own = 0, ev_pref = 0;
-  if (f.profile && !A.star && threadIdx.x < 64) {   // (how often the one consumer of the id prefix in this kernel runs)
-    const unsigned long long wm = __ballot(is_ev && !stamped);
-    if (threadIdx.x == 0 && wm) atomicAdd(&f.qclk_sh[KH_MATE_EV], (unsigned long long)__popcll(wm));
+  int mate_pref = acc_pref;   // (accepted samples below the workgroup of an event's round-mate neighbour)
+  if constexpr (!STAR) {
+    // Plain SFF: an event whose neighbour was accepted in this round needs that sample's node id for its stamp - the
+    // accepted samples of the workgroups below the neighbour's (bj <= b), from their KC_ACC words.  Rare, so
+    // only a workgroup that holds such an event waits for the lower workgroups at all: the first wavefront's ballot goes
+    // through LDS to all 1024 threads, then every thread brings one lower workgroup's count and each event gets a block
+    // sum over the lines below ITS neighbour's workgroup.
+    if (we != 0ULL) {
+      if (threadIdx.x < 64) {
+        const bool m = is_ev && !stamped;
+        int bj = b;
+        if (m) bj = (A.rec_nb[(size_t)e_i * A.nbcap + s_dk[threadIdx.x]] - Tb) >> 6;
+        const unsigned long long wm = __ballot(m), wx = __ballot(m && bj != b);
+        s_bj[threadIdx.x] = bj;
+        if (threadIdx.x == 0) {
+          s_wm = wm;
+          // (SFFGPU_PROFILE: how often this branch runs, and how often the neighbour sits in a lower workgroup)
+          if (f.profile && wm) atomicAdd(&f.qclk_sh[KH_MATE_EV], (unsigned long long)__popcll(wm) | ((unsigned long long)__popcll(wx) << 32));
+        }
+      }
+      __syncthreads();
+      const unsigned long long wm = s_wm;
+      if (wm != 0ULL) {
+        unsigned long long part = 0;
+        if ((int)threadIdx.x < b) part = kc_wait(f.wg_pub + (size_t)threadIdx.x * SFFK_PUB_WORDS + KC_ACC, seq, f.commit_seq + 6);
+        for (unsigned long long m = wm; m; m &= m - 1ULL) {
+          const int e = __ffsll((long long)m) - 1;
+          const int below = (int)kc_block_sum((int)threadIdx.x < s_bj[e] ? part : 0ULL, &s_sum);
+          if ((int)threadIdx.x == e) mate_pref = below;
+        }
+      }
+    }
   }
-  if (we != 0ULL || last) {
+  if (we != 0ULL || (STAR && last)) {
     if (is_ev && !stamped) {                 // (a round-mate neighbour was accepted: its new id)
       const int raw = A.rec_nb[(size_t)e_i * A.nbcap + s_dk[threadIdx.x]];
       const int j = raw - Tb, bj = j >> 6;
-      int pj = acc_pref;
+      int pj = mate_pref;
       unsigned long long wj = wa;
       if (bj != b) {
         const unsigned long long* pp = f.wg_pub + (size_t)bj * SFFK_PUB_WORDS;
-        pj = (int)kc_wait(pp + KC_PREF, seq, f.commit_seq + 6);
+        if constexpr (STAR) pj = (int)kc_wait(pp + KC_PREF, seq, f.commit_seq + 6);   // (plain SFF: nobody publishes it)
         wj = (unsigned long long)kc_wait(pp + KC_WLO, seq, f.commit_seq + 6) |
              ((unsigned long long)kc_wait(pp + KC_WHI, seq, f.commit_seq + 6) << 32);
       }
@@ -657,7 +699,7 @@ __global__ __launch_bounds__(1024) void k_commit(ResolveArgs A, int n_bound) {
       f.b_n1[at] = e_nb < e_ex ? e_nb : e_ex; f.b_n2[at] = e_nb < e_ex ? e_ex : e_nb;
       f.b_ta[at] = ta < tb ? ta : tb; f.b_tb[at] = ta < tb ? tb : ta;
       for (int q = 0; q < 6; ++q) pe6[q] = A.st.pos[6 * (size_t)e_ex + q];
-      if (A.star) {
+      if (STAR) {
         // SFF*: the two costs are the ones the sample's turn finds (earlier samples of the round may have rewired either
         // node): k_star_pass adds them to the distance
         const int e = at - nb0;
@@ -670,7 +712,7 @@ __global__ __launch_bounds__(1024) void k_commit(ResolveArgs A, int n_bound) {
     }
   }
   KC_TRACE(7);
-  if (last && !A.star && threadIdx.x == 0) {   // (for the profile line: written with the control block, by commit_finalize)
+  if (last && !STAR && threadIdx.x == 0) {   // (for the profile line: written with the control block, by commit_finalize)
     f.qclk_sh[KH_PASSES] = (unsigned long long)passes;
     if (clk) {
       tk[3] = wall_clock64();
@@ -703,7 +745,7 @@ __global__ __launch_bounds__(1024) void k_commit(ResolveArgs A, int n_bound) {
   // (deferred: every event counted - an upper bound until the append launch has entered the ones that own their key)
   const int n_acc = acc_pref + __popcll(wa), n_ev = defer ? (int)tot[7] : ev_pref + n_own;
   const bool faulted = s_ev_total != 0;
-  if (A.star && !faulted) {
+  if (STAR && !faulted) {
     // SFF*: the star stage may still fault after this kernel has committed the round's bookkeeping (a member edge's
     // candidate list, the fixed point's launch budget): the control block as a rolled-back round leaves it, for k_star_apply
     for (int w = threadIdx.x; w < (int)(sizeof(DevCtrl) / 4); w += 1024)
@@ -715,11 +757,11 @@ __global__ __launch_bounds__(1024) void k_commit(ResolveArgs A, int n_bound) {
     if (faulted) {
       commit_roll_back(&K);
       *A.fault_pending = 0;
-      if (A.star) { A.S.hdr[0] = 0; A.S.hdr[1] = 1; A.S.hdr[2] = 0; A.S.hdr[4] = 0; }
+      if (STAR) { A.S.hdr[0] = 0; A.S.hdr[1] = 1; A.S.hdr[2] = 0; A.S.hdr[4] = 0; }
     } else {
       commit_counters(K, tot, work_items, f.qclk_sh != nullptr, q_beg, q_end);
       commit_next_round(f, &K, n_acc, n_ev, false);   // (commit_next.h)
-      if (A.star) {
+      if (STAR) {
         K.nn_queries += (unsigned long long)n_acc;       // one knnSearch per accepted sample (src/forest.h:317)
         A.S.hdr[0] = n_acc; A.S.hdr[1] = 0; A.S.hdr[2] = n_ev; A.S.hdr[3] = nb0; A.S.hdr[4] = 0;
       }
@@ -819,45 +861,88 @@ __device__ __forceinline__ AppCtl hand_app_ctl(const HandIn& h, const CommitRegs
 // What the append has to apply, from the old block alone (commit_applied: no totals) - all that the workgroups which create
 // the nodes or enter the border events need.  new_cnt and wave_over are NOT the next round's.  Every thread of the
 // workgroup calls it behind hand_join (one barrier inside: every wavefront's first batch has returned).
-__device__ __forceinline__ AppCtl hand_applied(const ResolveArgs& A, const HandIn& h) {
+__device__ __forceinline__ AppCtl hand_applied(const ResolveArgs& A, const HandIn& h, bool counted_in = false) {
   if (!hand_ran(h)) { AppCtl a{}; a.ord_valid = h.ord_valid; return a; }
-  __syncthreads();
-  if (threadIdx.x == 0) hand_count_in(A);
+  if (!counted_in) {   // (behind hand_lines the workgroup has its barrier and is counted in)
+    __syncthreads();
+    if (threadIdx.x == 0) hand_count_in(A);
+  }
   CommitRegs k = h.k;
   commit_applied(&k, h.fault != 0);
   return hand_app_ctl(h, k);
 }
+// What a workgroup of the append launch keeps of the commit's lines in LDS: the totals of the lines' chunks of 64 (accepted
+// samples | border events << 32; commit_next.h: commit_prefix_base) and, for the four 64-sample groups its own 256
+// threads stand for, the accepted samples of the lower groups of the same chunk.
+struct HandLds {
+  unsigned long long part[SFFK_LINE_CHUNKS];
+  int pref[4];
+};
+// Inclusive sum over the wavefront's lanes in six data-parallel adds: within rows of 16 lanes (row_shr 1, 2, 4, 8; a lane
+// without a source adds 0), then lane 15 of rows 0 and 2 into rows 1 and 3 (row_bcast15), then lane 31 into the upper
+// half (row_bcast31).  A scan with __shfl_up is six trips through the LDS crossbar, each waited for; this one sits behind
+// the first batch of loads of every workgroup of the append launch.
+__device__ __forceinline__ unsigned wave_scan_add(unsigned v) {
+  int x = (int)v;
+  x += __builtin_amdgcn_update_dpp(0, x, 0x111, 0xf, 0xf, false);
+  x += __builtin_amdgcn_update_dpp(0, x, 0x112, 0xf, 0xf, false);
+  x += __builtin_amdgcn_update_dpp(0, x, 0x114, 0xf, 0xf, false);
+  x += __builtin_amdgcn_update_dpp(0, x, 0x118, 0xf, 0xf, false);
+  x += __builtin_amdgcn_update_dpp(0, x, 0x142, 0xa, 0xf, false);
+  x += __builtin_amdgcn_update_dpp(0, x, 0x143, 0xc, 0xf, false);
+  return (unsigned)x;
+}
+__device__ __forceinline__ int hand_chunks(int n_lines) {   // (a wave has SFFK_DEV_MAX_GROUPS lines at most: forest.cpp)
+  const int k = (n_lines + 63) >> 6;
+  return k < SFFK_LINE_CHUNKS ? k : SFFK_LINE_CHUNKS;
+}
+// The workgroup lines, one per thread (hand_request<true>; waves above 16 384 slots: 256 more per turn of the loop): a
+// line counts when it carries the commit's launch number (commit_line_count - the lines above the round's size are
+// stale), a wavefront scans its 64 lines with shuffles - accepted samples and border events in one register, 16 bits
+// each: 64 lines x 64 samples at most - and leaves its total and, where a line is one of the workgroup's own four groups
+// (g0 = the first of them), the line's prefix within the chunk.  ONE trip through LDS for the totals and the prefix; behind
+// its barrier every wavefront's first batch has returned and the workgroup counts itself in.  Every thread calls it
+// behind hand_join, in a round that ran (hand_ran: the same for every thread).
+__device__ __forceinline__ void hand_lines(const ResolveArgs& A, const HandIn& h, int n_lines, int g0, HandLds* s) {
+  const DevForestView& f = A.f;
+  const unsigned seq = (unsigned)h.seq0 + 1u;
+  const int lane = threadIdx.x & 63;
+  unsigned long long acc = h.acc, evn = h.evn;
+  // (the first 256 lines by all four wavefronts, whatever n_lines is: part[0..3] are always written, and read without a loop)
+  for (int l = threadIdx.x; l < 256 || l < 64 * hand_chunks(n_lines); l += 256) {   // (whole chunks: a wavefront stays together)
+    if (l >= 256) {
+      const unsigned long long* pp = f.wg_pub + (size_t)(l < n_lines ? l : 0) * SFFK_PUB_WORDS;
+      acc = pp[KC_ACC]; evn = pp[KC_EVN];
+    }
+    const unsigned pk = l < n_lines ? commit_line_count(acc, seq) | (commit_line_count(evn, seq) << 16) : 0u;
+    const unsigned inc = wave_scan_add(pk);
+    if ((unsigned)(l - g0) < 4u) s->pref[l - g0] = (int)((inc - pk) & 0xffffu);
+    if (lane == 63) s->part[l >> 6] = (unsigned long long)(inc & 0xffffu) | ((unsigned long long)(inc >> 16) << 32);
+  }
+  __syncthreads();
+  if (threadIdx.x == 0) hand_count_in(A);
+}
+// accepted samples before group g, one of the workgroup's own four (behind hand_lines)
+__device__ __forceinline__ int hand_prefix(const HandLds* s, int g) { return commit_prefix_base(s->part, g) + s->pref[g & 3]; }
 // The round's totals over the workgroup lines - a word counts when it carries this commit's launch number, the lines
 // above the round's size are stale - one trip through LDS; h.k then becomes the control block the finalize block writes
 // (commit_next_round).  Every thread of the workgroup calls it behind hand_join (one barrier inside, behind which the
 // workgroup counts itself in).
-__device__ __forceinline__ AppCtl hand_derive(const ResolveArgs& A, HandIn& h, int n_lines, unsigned long long* s_part) {
-  const DevForestView& f = A.f;
+__device__ __forceinline__ AppCtl hand_derive(const ResolveArgs& A, HandIn& h, int n_lines, int g0, HandLds* s) {
   if (!hand_ran(h)) { AppCtl a{}; a.ord_valid = h.ord_valid; return a; }
-  const unsigned seq = (unsigned)h.seq0 + 1u;
-  auto line = [&](unsigned long long acc, unsigned long long evn) -> unsigned long long {
-    return ((unsigned)(acc >> 32) == seq ? (unsigned long long)(unsigned)acc : 0ULL) |
-           ((unsigned)(evn >> 32) == seq ? (unsigned long long)(unsigned)evn << 32 : 0ULL);
-  };
-  unsigned long long v = (int)threadIdx.x < n_lines ? line(h.acc, h.evn) : 0ULL;   // (accepted | events << 32)
-  for (int t = threadIdx.x + 256; t < n_lines; t += 256) {   // (waves above 16 384 slots)
-    const unsigned long long* pp = f.wg_pub + (size_t)t * SFFK_PUB_WORDS;
-    v += line(pp[KC_ACC], pp[KC_EVN]);
-  }
-  // (a wavefront's share: 64 threads x 4 lines x 64 samples at most - 16 bits each, one register through the shuffles)
-  unsigned pk = (unsigned)v | ((unsigned)(v >> 32) << 16);
-  for (int off = 32; off > 0; off >>= 1) pk += __shfl_xor(pk, off);
-  if ((threadIdx.x & 63) == 0) s_part[threadIdx.x >> 6] = (unsigned long long)(pk & 0xffffu) | ((unsigned long long)(pk >> 16) << 32);
-  __syncthreads();
-  if (threadIdx.x == 0) hand_count_in(A);
-  v = s_part[0] + s_part[1] + s_part[2] + s_part[3];
-  commit_next_round(f, &h.k, (int)(unsigned)v, (int)(v >> 32), h.fault != 0);
+  hand_lines(A, h, n_lines, g0, s);
+  unsigned long long v = s->part[0] + s->part[1] + s->part[2] + s->part[3];   // (accepted | events << 32)
+  for (int k = 4; k < hand_chunks(n_lines); ++k) v += s->part[k];              // (waves above 16 384 slots)
+  commit_next_round(A.f, &h.k, (int)(unsigned)v, (int)(v >> 32), h.fault != 0);
   return hand_app_ctl(h, h.k);
 }
 __device__ __forceinline__ void append_ord_store(const ResolveArgs& A, const AppCtl& C, int ord_at, int next) {
   if (ord_at >= 0) (C.act_sel ? A.f.ord.lst[0] : A.f.ord.lst[1])[ord_at] = next;
 }
-__device__ __forceinline__ int append_one(const ResolveArgs& A, const AppCtl& C, int i, int& slot_out, int& ord_at, int part = 0) {
+// hs: plain SFF - the workgroup's share of the commit's lines (hand_lines: the accepted samples before a group of the
+// workgroup's own); SFF* (nullptr): k_commit has written the prefix, acc_pref.
+__device__ __forceinline__ int append_one(const ResolveArgs& A, const AppCtl& C, const HandLds* hs, int i, int& slot_out, int& ord_at,
+                                          int part = 0) {
   ord_at = -1;
   const DevForestView& f = A.f;
   const int n = C.n;
@@ -888,7 +973,7 @@ __device__ __forceinline__ int append_one(const ResolveArgs& A, const AppCtl& C,
     return -1;
   }
   const unsigned long long w = f.w_acc[i >> 6];
-  const int rank = f.acc_pref[i >> 6] + __popcll(w & ((1ULL << (i & 63)) - 1ULL));
+  const int rank = (hs ? hand_prefix(hs, i >> 6) : f.acc_pref[i >> 6]) + __popcll(w & ((1ULL << (i & 63)) - 1ULL));
   if (!((w >> (i & 63)) & 1ULL)) {
     // its sample's index in the next round joins the list of its sub-range (OrderView): a returning atomic behind two
     // dependent loads - in k_append_sample the NODE-creating half of the workgroups does it (for a sample that was not
@@ -1111,7 +1196,7 @@ __device__ void commit_finalize(const ResolveArgs& A, int others, bool sampler) 
   }
 }
 __global__ __launch_bounds__(256) void k_append(ResolveArgs A, int append_blocks, int n_lines) {
-  __shared__ unsigned long long s_hand[4];
+  __shared__ HandLds s_hand;
   if (!A.star && blockIdx.x == gridDim.x - 1) { commit_finalize(A, (int)gridDim.x - 1, false); return; }
   const bool border = (int)blockIdx.x >= append_blocks;
   AppCtl C;
@@ -1120,14 +1205,14 @@ __global__ __launch_bounds__(256) void k_append(ResolveArgs A, int append_blocks
     HandIn h = hand_request<false>(A, n_lines);
     hand_join(h);
     C = hand_applied(A, h);
-  } else {   // (the next round's list length, the claims of a wave that is over: the totals)
+  } else {   // (node ids and list places: the lines' prefix; the next round's list length, the claims of a wave that is over: the totals)
     HandIn h = hand_request<true>(A, n_lines);
     hand_join(h);
-    C = hand_derive(A, h, n_lines, s_hand);
+    C = hand_derive(A, h, n_lines, 4 * (int)blockIdx.x, &s_hand);
   }
   if (border) { border_finalize(A, C, (int)blockIdx.x - append_blocks); return; }
   int slot, ord_at;
-  const int next = append_one(A, C, blockIdx.x * 256 + threadIdx.x, slot, ord_at);
+  const int next = append_one(A, C, A.star ? nullptr : &s_hand, blockIdx.x * 256 + threadIdx.x, slot, ord_at);
   append_ord_store(A, C, ord_at, next);
 }
 // The sampling workgroups' share of the commit: the next round's active list (+ the claims of a wave that is over), and
@@ -1142,7 +1227,7 @@ __global__ __launch_bounds__(256) void k_append(ResolveArgs A, int append_blocks
 // Plain SFF: the control-block fields are the ones the commit found.  Which slot draws which sample needs the
 // committed round's size and list only (commit_applied); the next round's size, list length and "the wave is over" come
 // from the round's totals (hand_derive, in the kernel) - the stores and the sample's second batch wait for them.
-struct ListOne { int i, n, act_cnt, app_sel, new_cnt, slot, ex, next; bool wave_over; };
+struct ListOne { int i, n, act_cnt, app_sel, new_cnt, slot, ex, next, pref; unsigned long long w; bool wave_over; };
 __device__ __forceinline__ void append_list_request(const ResolveArgs& A, int i, int bound, int n_lines, HandIn& h, SampleCtl& K,
                                                     ListOne& L) {
   const DevForestView& f = A.f;
@@ -1150,7 +1235,7 @@ __device__ __forceinline__ void append_list_request(const ResolveArgs& A, int i,
   const int ic = i < bound ? i : bound - 1;
   if (!A.star) h = hand_request<true>(A, n_lines);
   unsigned long long w = f.w_acc[ic >> 6];
-  int pref = f.acc_pref[ic >> 6];
+  int pref = A.star ? f.acc_pref[ic >> 6] : 0;   // (plain SFF: from the lines, behind hand_derive)
   int s0 = f.act_slot[ic], s1 = f.act_slot2[ic];
   int ex = A.parent[ic];
   L.i = i; L.n = 0; L.act_cnt = 0; L.app_sel = 0; L.new_cnt = 0; L.wave_over = false;
@@ -1164,7 +1249,7 @@ __device__ __forceinline__ void append_list_request(const ResolveArgs& A, int i,
     L.wave_over = K.n == 0 && !K.halt && in_wave && !use_closed;
   } else {
     hand_join(h);
-    join_v(w, pref, s0, s1, ex);
+    join_v(w, s0, s1, ex);
     K = SampleCtl{};
     K.words_base = h.k.cursor;   // (a next round's words start where the cursor stands)
     if (hand_ran(h)) {
@@ -1175,9 +1260,14 @@ __device__ __forceinline__ void append_list_request(const ResolveArgs& A, int i,
   }
   L.slot = L.app_sel ? s1 : s0;
   L.ex = ex;
-  // not accepted: the slot tries again - the accepted samples before it leave the list (accepted: the node-creating
-  // workgroups, SFF*: k_star_apply, have it)
-  L.next = (i < L.n && !((w >> (i & 63)) & 1ULL)) ? i - (pref + __popcll(w & ((1ULL << (i & 63)) - 1ULL))) : -1;
+  L.w = w; L.pref = pref; L.next = -1;
+}
+// not accepted: the slot tries again - the accepted samples before it leave the list (accepted: the node-creating
+// workgroups, SFF*: k_star_apply, have it).  L.pref = the accepted samples before the slot's group: SFF* from k_commit's
+// acc_pref (append_list_request), plain SFF from the commit's lines (hand_prefix, behind hand_derive).
+__device__ __forceinline__ void append_list_next(ListOne& L) {
+  const int i = L.i;
+  L.next = (i < L.n && !((L.w >> (i & 63)) & 1ULL)) ? i - (L.pref + __popcll(L.w & ((1ULL << (i & 63)) - 1ULL))) : -1;
 }
 __device__ __forceinline__ void append_list_store(const ResolveArgs& A, const ListOne& L) {
   const DevForestView& f = A.f;
@@ -1208,21 +1298,27 @@ __device__ __forceinline__ void append_list_store(const ResolveArgs& A, const Li
 // The first half of the workgroups creates the accepted samples' nodes, the second half writes the list and samples: a
 // wavefront that had to do both would run the two chains of dependent loads one after the other.
 __global__ __launch_bounds__(256) void k_append_sample(ResolveArgs A, SampleLaunch P, int append_blocks, int n_lines) {
-  __shared__ unsigned long long s_hand[4];
+  __shared__ HandLds s_hand;
   if (!A.star && blockIdx.x == gridDim.x - 1) { commit_finalize(A, (int)gridDim.x - 1, true); return; }
   const int nb = append_blocks;
   const bool sampler = (int)blockIdx.x >= nb && (int)blockIdx.x < 2 * nb;
   if (!sampler) {
+    const bool border = (int)blockIdx.x >= 2 * nb;
     AppCtl C;
     if (A.star) C = app_ctl_block(A.f);
-    else {   // (node ids, frontier places, iteration stamps, border entries: nothing of the round's totals)
+    else if (border) {   // (border entries: nothing of the round's totals, no node ids)
       HandIn h = hand_request<false>(A, n_lines);
       hand_join(h);
       C = hand_applied(A, h);
+    } else {   // (node ids and frontier places: the lines' prefix, in the same batch as the block's fields; no totals)
+      HandIn h = hand_request<true>(A, n_lines);
+      hand_join(h);
+      if (hand_ran(h)) hand_lines(A, h, n_lines, 4 * (int)blockIdx.x, &s_hand);
+      C = hand_applied(A, h, true);
     }
-    if ((int)blockIdx.x >= 2 * nb) { border_finalize(A, C, (int)blockIdx.x - 2 * nb); return; }
+    if (border) { border_finalize(A, C, (int)blockIdx.x - 2 * nb); return; }
     int slot, ord_at;
-    (void)append_one(A, C, blockIdx.x * 256 + threadIdx.x, slot, ord_at, 1);
+    (void)append_one(A, C, A.star ? nullptr : &s_hand, blockIdx.x * 256 + threadIdx.x, slot, ord_at, 1);
     return;
   }
   const int tid = ((int)blockIdx.x - nb) * 256 + threadIdx.x;
@@ -1231,11 +1327,13 @@ __global__ __launch_bounds__(256) void k_append_sample(ResolveArgs A, SampleLaun
   ListOne L;
   append_list_request(A, tid, P.n, n_lines, h, K, L);
   if (!A.star) {
-    const AppCtl C = hand_derive(A, h, n_lines, s_hand);
+    const AppCtl C = hand_derive(A, h, n_lines, 4 * ((int)blockIdx.x - nb), &s_hand);
+    if (tid < L.n) L.pref = hand_prefix(&s_hand, tid >> 6);   // (L.n > 0: the round ran, the lines are in)
     K.n = h.k.n_act; K.halt = h.k.halt; K.act_sel = h.k.act_sel; K.round = h.k.round;
     K.ord_valid = h.ord_valid; K.n_slots = h.n_slots; K.act_identity = h.act_identity;
     L.new_cnt = C.new_cnt; L.wave_over = C.wave_over != 0;
   }
+  append_list_next(L);
   append_list_store(A, L);
   if (K.halt) return;
   const bool valid = L.next >= 0 && L.next < K.n;
@@ -1532,7 +1630,8 @@ void launch_wave_begin_only(hipStream_t s, const DevForestView& f) {
 }
 void launch_commit(hipStream_t s, const ResolveArgs& a, int n_bound, const StarLaunch* star, const SampleLaunch* next) {
   if (n_bound <= 0) return;
-  hipLaunchKernelGGL(k_commit, dim3((n_bound + 63) / 64), dim3(1024), 0, s, a, n_bound);
+  if (a.star) hipLaunchKernelGGL(k_commit<true>, dim3((n_bound + 63) / 64), dim3(1024), 0, s, a, n_bound);
+  else hipLaunchKernelGGL(k_commit<false>, dim3((n_bound + 63) / 64), dim3(1024), 0, s, a, n_bound);
   if (a.star && star) launch_star_stage(s, a, n_bound, *star);
   // (plain SFF: + one workgroup per 64 samples that enters the round's border events, border_finalize, + the finalize
   // block that writes the control block, commit_finalize: the highest index)

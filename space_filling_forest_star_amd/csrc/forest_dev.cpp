@@ -1757,10 +1757,10 @@ void Forest::run_device(int max_waves) {
     // loads included; SFF*: by k_commit's last workgroup, as part of that kernel's critical path)
     fprintf(stderr, "[sffgpu k_commit us/commit, last workgroup] walks + waits for earlier samples %.1f (%.2f polls, max %llu) "
             "lower workgroups' counts %.1f borders %.1f | control block (%s) %.1f | dependent/round %.0f | "
-            "border events with a neighbour accepted in the same round %llu\n", k.prof[0] / r / 100.0, k.prof[5] / r,
+            "border events with a neighbour accepted in the same round %llu, in a lower workgroup %llu\n", k.prof[0] / r / 100.0, k.prof[5] / r,
             (unsigned long long)k.prof[7], k.prof[1] / r / 100.0, k.prof[2] / r / 100.0,
             cfg.optimize ? "in k_commit" : "finalize block of the append launch", k.prof[3] / r / 100.0,
-            (double)k.n_unsettled / r, (unsigned long long)k.prof[4]);
+            (double)k.n_unsettled / r, (unsigned long long)(k.prof[4] & 0xffffffffULL), (unsigned long long)(k.prof[4] >> 32));
 #ifdef SFFK_CI_TRACE
     {
       std::vector<unsigned long long> tr(4096 * 8);

@@ -178,7 +178,8 @@ struct DevCtrl {
   // k_commit phase clocks (wall_clock64 ticks of 10 ns, thread 0 of the round's LAST workgroup, SFFGPU_PROFILE only):
   // walks + waits for earlier samples, lower workgroups' counts (ids), borders, totals + control block (plain SFF: the
   // clock of the append launch's finalize block, which writes the block); [4] = plain SFF: border events whose neighbour
-  // was accepted in the same round; [5] = polls of the walk phase, [6] = commits, [7] = most polls
+  // was accepted in the same round (low half) and, of them, those whose neighbour sits in a lower commit workgroup (high
+  // half); [5] = polls of the walk phase, [6] = commits, [7] = most polls
   unsigned long long prof[8];
   // device-clock bracket of the neighbour-query kernel of the current round (first wave in .. last wave out, 100 MHz
   // wall_clock64 ticks) and its sum over all committed rounds: the duration rocprofv3 reports, without the ~3 us a
@@ -510,8 +511,9 @@ struct DevForestView {
   int32_t temp_base;           // store index of the round's temporaries
   int32_t goal_id;             // Problem::hasGoal: the goal's node (a one-node tree that is searched, never expanded), -1 = none
   int32_t* ulist;              // scratch list of a wave's slots (k_wave_end)
-  // one 64-bit word per 64 samples: the accepted samples, and how many were accepted before the word (k_commit ->
-  // k_append_sample / the star stage: node ids and the next round's active list without walking the samples)
+  // one 64-bit word per 64 samples: the accepted samples, and - SFF* only - how many were accepted before the word
+  // (k_commit -> k_append_sample / the star stage: node ids and the next round's active list without walking the
+  // samples; plain SFF: the append launch derives the prefix from the workgroups' lines, commit_next.h)
   unsigned long long* w_acc; int32_t* acc_pref;
   // border events of a round (plain SFF: entered by the append launch): the samples with an event, per 64 samples; per
   // sample the table entry its stamp went to, the neighbour's node id and the raw neighbour (store id or temporary)
