@@ -70,6 +70,20 @@ typedef struct {
 } sffgpu_ctx_memory;
 int sffgpu_ctx_get_memory(sffgpu_ctx* ctx, sffgpu_ctx_memory* out);
 
+/* 1 while the context's node grid is COMPACT, 0 otherwise (SFFGPU_ERR_ARG: NULL).
+ * A member created while SFFGPU_COMPACT_GRID=1 starts compact; sffgpu_create contexts never are, and later values of the
+ * variable change nothing.  The dense grid gives every cell of the limits' box a bucket of 8 node items with their filter
+ * records (about 0.6 GB on a 100 x 100 x 50 box at the usual cell edge, whatever the node count).  The compact grid keeps
+ * two 4-byte words per cell and takes the buckets - fp64 items only - from a pool as large as the node store: the first
+ * node of a cell opens its bucket; a pool that runs out sends items to the overflow list, which every query scans, and is
+ * doubled at the next check.  Results are the same in both layouts.
+ * Only forest batches, session batches and runs of the same one-wavefront loop (sffgpu_forest_run of an eligible forest
+ * under SFFGPU_SPEC=0) work on a compact grid.  Everything else that reads the node grid first makes it dense, on the
+ * host, before it launches: a forest with wave > 1, the speculative kernel of a wave-1 forest, a wave handed to the
+ * host-replay engine, the multi-GPU round protocol, sffgpu_nodes_index / sffgpu_knn, an RRT session's host loop once it
+ * queries by grid.  The context then stays dense - this function returns 0 and grid_bytes has grown. */
+int sffgpu_ctx_grid_compact(sffgpu_ctx* ctx);
+
 /* Poses.  Wherever the caller hands in poses (x y z yaw pitch roll) - sffgpu_collide_poses, sffgpu_collide_segments, the
  * centres of sffgpu_sample_steer, the roots and the goal of sffgpu_forest_create / sffgpu_rrt_create - every coordinate
  * must be finite and every angle must lie within +-2^20 * pi/2 (about 1.647e6; SFFP_TRIG_DOMAIN of csrc/sff_pmath.h),

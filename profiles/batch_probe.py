@@ -19,6 +19,10 @@ seeds; the clock is the host's, around calls that end in a synchronisation.  App
       (member contexts: on THIS build context 0 uploads and the others are made with sffgpu_create_member; a parent build,
        which has no such entry point, sets every context up in full as before)
 
+  python profiles/batch_probe.py --parent-lib ... --legs a --a-builds new,compact --batch-sizes 64,128,256 --share-env
+      (the compact node grid: build "compact" is this build with its members created under SFFGPU_COMPACT_GRID=1, alternated
+       with the dense members of "new"; --compact makes the members of "new" compact too)
+
 Every record of leg a also carries the set-up: setup_seconds = the wall time of the contexts (first sffgpu_create to the
 last context ready) + that of creating the measured forests, and - a build that has sffgpu_ctx_get_memory - memory_member_1,
 Context.memory() of member 1 after the run.
@@ -60,7 +64,10 @@ def child(a):
     t_setup = time.perf_counter()
     for _ in range(n_ctx - 1):
         if a.share_env:
+            if a.compact:   # (sffgpu_create_member reads the knob, and nothing after it does)
+                os.environ["SFFGPU_COMPACT_GRID"] = "1"
             c = ctx0.member()
+            os.environ.pop("SFFGPU_COMPACT_GRID", None)
         else:
             c = S.Context(0)
             c.upload_env(sc["env"])
@@ -114,6 +121,8 @@ def child(a):
         "share_env": bool(a.share_env), "setup_contexts_seconds": setup_ctx, "setup_forests_seconds": setup_forests,
         "setup_seconds": None if setup_forests is None else setup_ctx + setup_forests,
         "memory_member_1": ctxs[1].memory() if n_ctx > 1 and hasattr(S.lib(), "sffgpu_ctx_get_memory") else None,
+        "compact": bool(a.compact), "grid_rebuilds": sum(s["grid_rebuilds"] for s in stats),
+        "members_still_compact": (sum(c.grid_compact() for c in ctxs[1:]) if a.compact else None),
         "fingerprints": ["%016x" % x for x in fps]}), flush=True)
 
 
@@ -138,6 +147,7 @@ def main():
     ap.add_argument("--a-builds", default="new")      # leg a; "new,parent": the parent's run_batch too (a parent that has one)
     ap.add_argument("--b-builds", default="parent")   # leg b; "new,parent": this build's Forest.run too, alternated
     ap.add_argument("--share-env", action="store_true")   # leg a, this build: contexts 1.. are members of context 0
+    ap.add_argument("--compact", action="store_true")     # with --share-env: the members are created under SFFGPU_COMPACT_GRID=1
     ap.add_argument("--child-timeout", type=int, default=420)
     ap.add_argument("--out", default=OUT)
     a = ap.parse_args()
@@ -160,14 +170,17 @@ def main():
                 env = dict(os.environ)
                 env.pop("SFFGPU_LIB", None)
                 env.pop("SFFGPU_SPEC", None)
+                env.pop("SFFGPU_COMPACT_GRID", None)
                 if build == "parent":
                     env["SFFGPU_LIB"] = os.path.abspath(a.parent_lib)
                 if leg == "c":
                     env["SFFGPU_SPEC"] = "0"
                 cmd = [sys.executable, os.path.abspath(__file__), "--child", "--leg", leg, "--build", build, "--B", str(B),
                        "--optimize", str(opt), "--repeat", str(rep), "--budget", str(a.budget)]
-                if a.share_env and leg == "a" and build == "new":
+                if a.share_env and leg == "a" and build in ("new", "compact"):
                     cmd.append("--share-env")
+                    if a.compact or build == "compact":
+                        cmd.append("--compact")
                 p = subprocess.run(cmd, env=env, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True, timeout=a.child_timeout)
                 lines = [ln for ln in p.stdout.splitlines() if ln.startswith("RESULT ")]
                 if p.returncode != 0 or not lines:

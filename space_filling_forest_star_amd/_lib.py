@@ -26,7 +26,7 @@ EXPORTED_SYMBOLS = [
     "sffgpu_forest_run_batch", "sffgpu_rrt_run_batch",
     "sffgpu_forest_smooth_paths_batch", "sffgpu_rrt_smooth_paths_batch", "sffgpu_forest_get_smooth_stats",
     "sffgpu_rrt_get_smooth_stats",
-    "sffgpu_create_member", "sffgpu_ctx_get_memory",
+    "sffgpu_create_member", "sffgpu_ctx_get_memory", "sffgpu_ctx_grid_compact",
 ]
 
 # sffgpu_allgather_fn: int fn(void* user, const void* send_dev, void* recv_dev, size_t words_i32, void* hip_stream)
@@ -207,6 +207,8 @@ def lib():
     if hasattr(L, "sffgpu_create_member"):   # (SFFGPU_LIB may name a build from before member contexts; member() says so)
         L.sffgpu_create_member.argtypes = [C.c_void_p, C.POINTER(C.c_void_p)]
         L.sffgpu_ctx_get_memory.argtypes = [C.c_void_p, C.POINTER(CtxMemory)]
+    if hasattr(L, "sffgpu_ctx_grid_compact"):   # (... or from before the compact node grid; grid_compact() says so)
+        L.sffgpu_ctx_grid_compact.argtypes = [C.c_void_p]
     _LIB = L
     return L
 
@@ -261,6 +263,13 @@ class Context:
         m = CtxMemory()
         self._chk(self._L.sffgpu_ctx_get_memory(self.h, C.byref(m)))
         return m.as_dict()
+
+    def grid_compact(self):
+        """1 while this context's node grid is compact (a member created under SFFGPU_COMPACT_GRID=1 that nothing has
+        made dense yet: sffgpu_ctx_grid_compact), 0 otherwise"""
+        if not hasattr(self._L, "sffgpu_ctx_grid_compact"):
+            raise SffGpuError("this build of libsffgpu has no sffgpu_ctx_grid_compact")
+        return int(self._chk(self._L.sffgpu_ctx_grid_compact(self.h)))
 
     def close(self):
         if getattr(self, "h", None):

@@ -186,6 +186,11 @@ int sffgpu_create_member(sffgpu_ctx* owner, sffgpu_ctx** out) {
   }
 }
 
+int sffgpu_ctx_grid_compact(sffgpu_ctx* ctx) {
+  if (!ctx) return SFFGPU_ERR_ARG;
+  return ctx->c->grid_compact ? 1 : 0;
+}
+
 int sffgpu_ctx_get_memory(sffgpu_ctx* ctx, sffgpu_ctx_memory* out) {
   if (!ctx || !out) return SFFGPU_ERR_ARG;
   ctx->c->memory(out);
@@ -248,6 +253,7 @@ int sffgpu_nodes_index(sffgpu_ctx* ctx, const double limits[6], double cell) {
     c.grid_bk = 8;
     c.grid_cell0 = cell;
     c.grid_rebuilds = 0;
+    c.grid_compact = false;   // (the index's consumers - sffgpu_knn - read the dense layout)
     c.grid_setup(limits, cell);
     c.grid_insert_new();
     c.grid_check(/*bulk=*/true);

@@ -1630,6 +1630,7 @@ void launch_wave_begin_only(hipStream_t s, const DevForestView& f) {
 }
 void launch_commit(hipStream_t s, const ResolveArgs& a, int n_bound, const StarLaunch* star, const SampleLaunch* next) {
   if (n_bound <= 0) return;
+  grid_dense_only(a.g, "k_commit");   // (the round engine's grid: its queries read the filter records)
   if (a.star) hipLaunchKernelGGL(k_commit<true>, dim3((n_bound + 63) / 64), dim3(1024), 0, s, a, n_bound);
   else hipLaunchKernelGGL(k_commit<false>, dim3((n_bound + 63) / 64), dim3(1024), 0, s, a, n_bound);
   if (a.star && star) launch_star_stage(s, a, n_bound, *star);

@@ -718,6 +718,7 @@ void launch_star_stage(hipStream_t s, const ResolveArgs& a, int n_bound, const S
   const int sample_blocks = (n_bound + 3) / 4;
   int R0 = (int)std::ceil(L.cube_reach / L.cell_edge);
   R0 = R0 < 2 ? 2 : (R0 > STAR_R0_MAX ? STAR_R0_MAX : R0);
+  grid_dense_only(L.g, "k_star_knn");
   if (L.knn_lone) hipLaunchKernelGGL(k_star_knn, dim3(sample_blocks), dim3(256), 0, s, a, L.g, L.tg, L.st, L.cell_edge, L.slack, R0);
   else launch_star_knn_wg(s, a, L.g, L.tg, L.st, L.cell_edge, L.slack, n_bound, R0);
   const int event_blocks = (n_bound + 255) / 256;

@@ -169,6 +169,7 @@ Ctx::Ctx(int dev, const Ctx* owner) : device(dev) {
     robv = owner->robv;
     env_built_here = false;
     round_lazy = true;
+    grid_compact = kn.compact_grid;   // (decided here, once: Ctx::grid_compact)
   } else {
     env = std::make_shared<EnvBlock>(dev);
   }
@@ -263,7 +264,7 @@ Ctx::~Ctx() {
   for (auto e : pool) (void)hipEventDestroy(e);
   DevBuf* bufs[] = {&sx, &sy, &sz, &syaw, &spitch, &sroll, &stree, &spos,
                     &d_a, &d_b, &d_c, &d_d, &d_e, &d_f, &d_g, &d_h, &r_in, &r_out, &r_out2, &r_q, &r_cnt,
-                    &r_sega, &r_segb, &r_items, &r_items2, &r_center, &r_qrec, &g_cnt, &g_items, &g_ovfcnt, &g_ovf, &t_cnt, &t_items, &t_ovfcnt, &t_ovf, &t_occ, &g_lite, &g_ovf_lite, &t_lite, &t_ovf_lite, &r_sub, &rr_q1, &rr_q2, &rr_a, &rr_out, &rr_sq, &rr_np, &rr_alt, &rr_q2b, &rr_sqb, &seg_job[0].ids, &seg_job[0].a, &seg_job[0].b, &seg_job[0].c, &seg_job[1].ids, &seg_job[1].a,
+                    &r_sega, &r_segb, &r_items, &r_items2, &r_center, &r_qrec, &g_cnt, &g_items, &g_ovfcnt, &g_ovf, &g_bucket, &t_cnt, &t_items, &t_ovfcnt, &t_ovf, &t_occ, &g_lite, &g_ovf_lite, &t_lite, &t_ovf_lite, &r_sub, &rr_q1, &rr_q2, &rr_a, &rr_out, &rr_sq, &rr_np, &rr_alt, &rr_q2b, &rr_sqb, &seg_job[0].ids, &seg_job[0].a, &seg_job[0].b, &seg_job[0].c, &seg_job[1].ids, &seg_job[1].a,
                     &seg_job[1].b, &seg_job[1].c, &seg_job[2].ids, &seg_job[2].a, &seg_job[2].b, &seg_job[2].c, &seg_job[3].ids, &seg_job[3].a,
                     &seg_job[3].b, &seg_job[3].c, &sm_dev};
   for (DevBuf* b : bufs) b->release();
@@ -672,11 +673,15 @@ void Ctx::store_reserve(int capacity) {
   stree.ensure((size_t)cap * sizeof(int32_t));
   spos.ensure((size_t)cap * 6 * sizeof(double));
   store_cap = cap;
+  // (a compact grid: the pool follows the store at the grid's next rebuild - until then the nodes beyond it lie on the
+  // overflow list, whose length is what asks for that rebuild, grid_check)
+  if (grid_compact && kn.test_grid_pool <= 0) grid_pool_next = std::max(grid_pool_next, cap);
 }
 void Ctx::store_reset(int capacity) {
   store_n = 0;
   grid_on = false;
   grid_inserted = 0;
+  grid_pool_next = 0;
   store_maxabs = 1.0;
   store_reserve(std::max(capacity, 1024));
 }
@@ -717,6 +722,7 @@ void Ctx::store_set_tree(const int32_t* ids, int n, int32_t tree) {
     memcpy(lim, grid_limits, sizeof lim);
     grid_setup(lim, grid_cell);
     grid_insert_new();
+    if (grid_compact) ++grid_rebuilds;
     grid_check(/*bulk=*/true);
   }
 }
@@ -747,22 +753,39 @@ void Ctx::grid_setup(const double limits[6], double cell) {
   gridv.ovf_cap = gridv_ovf_cap_next;
   if (kn.test_grid_ovf >= 0) gridv.ovf_cap = std::max(gridv.ovf_cap / 65536 * kn.test_grid_ovf, kn.test_grid_ovf);  // tests: tiny list
   g_cnt.ensure(ncells * sizeof(int32_t));
-  g_items.ensure(ncells * gridv.bk * sizeof(sffk::GridItem));
   g_ovfcnt.ensure(16);
   g_ovf.ensure((size_t)gridv.ovf_cap * sizeof(sffk::GridItem));
-  g_lite.ensure(ncells * gridv.bk * sizeof(sffk::GridItem32));
-  g_ovf_lite.ensure((size_t)gridv.ovf_cap * sizeof(sffk::GridItem32));
+  if (grid_compact) {
+    // buckets from a pool as large as the store (a node opens at most one), or what grid_check asked for after the pool
+    // ran out; tests: a first pool of SFFGPU_TEST_GRID_POOL buckets, so that it does run out
+    int pool = grid_pool_next > 0 ? grid_pool_next : (kn.test_grid_pool > 0 ? kn.test_grid_pool : store_cap);
+    if (kn.test_grid_pool <= 0) pool = std::max(pool, store_cap);
+    grid_pool = grid_pool_next = std::max(pool, 1);
+    g_bucket.ensure(ncells * sizeof(int32_t));
+    g_items.ensure((size_t)grid_pool * gridv.bk * sizeof(sffk::GridItem));
+    HIPCHK(hipMemsetAsync(g_bucket.p, 0xff, ncells * sizeof(int32_t), stream));   // -1 = no bucket yet
+    gridv.bucket = g_bucket.as<int32_t>();
+    gridv.pool_cnt = g_ovfcnt.as<int32_t>() + 1;
+    gridv.pool_cap = grid_pool;
+  } else {
+    g_items.ensure(ncells * gridv.bk * sizeof(sffk::GridItem));
+    g_lite.ensure(ncells * gridv.bk * sizeof(sffk::GridItem32));
+    g_ovf_lite.ensure((size_t)gridv.ovf_cap * sizeof(sffk::GridItem32));
+    gridv.lite = g_lite.as<sffk::GridItem32>();
+    gridv.ovf_lite = g_ovf_lite.as<sffk::GridItem32>();
+  }
   HIPCHK(hipMemsetAsync(g_cnt.p, 0, ncells * sizeof(int32_t), stream));
   HIPCHK(hipMemsetAsync(g_ovfcnt.p, 0, 16, stream));
   gridv.cnt = g_cnt.as<int32_t>();
   gridv.items = g_items.as<sffk::GridItem>();
   gridv.ovf_cnt = g_ovfcnt.as<int32_t>();
   gridv.ovf = g_ovf.as<sffk::GridItem>();
-  gridv.lite = g_lite.as<sffk::GridItem32>();
-  gridv.ovf_lite = g_ovf_lite.as<sffk::GridItem32>();
   // the round's own grid: same cells, its own buckets / overflow list, all counters zero between rounds.  Here its
   // geometry and the counter the wave-end launches and status blocks read; the rest in round_grid()
   tgridv = gridv;
+  tgridv.bucket = nullptr;   // (the round grid is never compact - and a compact context has none)
+  tgridv.pool_cnt = nullptr;
+  tgridv.pool_cap = 0;
   tgridv.bk = 8;
   tgridv.ovf_cap = std::max(1 << 20, tgrid_ovf_min);   // >= the samples of one round (Forest::Forest)
   tgridv.cnt = nullptr;
@@ -780,8 +803,21 @@ void Ctx::grid_setup(const double limits[6], double cell) {
   round_ready = false;
   if (!round_lazy || had_round) round_grid();   // (a member context: only once a round engine has asked for it)
 }
+// compact -> dense, for good (engine.h, grid_compact): what store_set_tree does for a tree merge, in the other layout
+void Ctx::grid_dense() {
+  if (!grid_compact) return;
+  grid_compact = false;
+  if (!grid_on) return;
+  sync();
+  double lim[6];
+  memcpy(lim, grid_limits, sizeof lim);
+  grid_setup(lim, grid_cell);
+  grid_insert_new();
+  grid_check(/*bulk=*/true);
+}
 void Ctx::round_grid() {
   if (round_ready || !grid_on) return;
+  if (grid_compact) throw HipError{"round grid asked for on a compact node grid (grid_dense() comes first)"};
   HIPCHK(hipSetDevice(device));
   const size_t ncells = (size_t)tgridv.nx * tgridv.ny * tgridv.nz;
   t_cnt.ensure(ncells * sizeof(int32_t));
@@ -807,7 +843,7 @@ void Ctx::memory(sffgpu_ctx_memory* out) const {
   out->env_bytes = env_built_here ? (uint64_t)env->device_bytes() : 0;
   out->env_holders = (uint64_t)env.use_count();
   out->store_bytes = sum({&sx, &sy, &sz, &syaw, &spitch, &sroll, &stree, &spos});
-  out->grid_bytes = sum({&g_cnt, &g_items, &g_ovfcnt, &g_ovf, &g_lite, &g_ovf_lite, &t_ovfcnt});
+  out->grid_bytes = sum({&g_cnt, &g_items, &g_ovfcnt, &g_ovf, &g_lite, &g_ovf_lite, &t_ovfcnt, &g_bucket});
   out->round_grid_bytes = sum({&t_cnt, &t_items, &t_ovf, &t_occ, &t_lite, &t_ovf_lite});
   out->other_bytes = sum({&d_a, &d_b, &d_c, &d_d, &d_e, &d_f, &d_g, &d_h, &sm_dev, &r_in, &r_out, &r_q, &r_cnt, &r_sega, &r_segb,
                           &r_items, &r_items2, &r_sub, &r_center, &r_qrec, &r_out2, &rr_q1, &rr_q2, &rr_a, &rr_out, &rr_sq, &rr_np, &rr_alt, &rr_q2b, &rr_sqb});
@@ -825,6 +861,25 @@ void Ctx::grid_insert_new() {
 void Ctx::grid_check(bool bulk) {
   if (!grid_on) return;
   int32_t v = 0;
+  if (grid_compact) {
+    // a compact grid first looks at its pool: when that ran out, the list filled up for want of buckets, not of room in
+    // the cells - twice the pool (at least the store's capacity), same cell edge, until the nodes' cells all have one
+    int32_t w[2] = {0, 0};
+    HIPCHK(hipMemcpyAsync(w, g_ovfcnt.p, 8, hipMemcpyDeviceToHost, stream));
+    HIPCHK(hipStreamSynchronize(stream));
+    for (int tries = 0; tries < 32 && w[1] > grid_pool; ++tries) {
+      if (!bulk && w[0] > gridv.ovf_cap) throw HipError{"neighbour grid overflow list exhausted during a wave (nodes were dropped)"};
+      grid_pool_next = std::max(2 * grid_pool, kn.test_grid_pool > 0 ? 0 : store_cap);
+      double lim[6];
+      memcpy(lim, grid_limits, sizeof lim);
+      grid_setup(lim, grid_cell);
+      grid_insert_new();
+      ++grid_rebuilds;
+      bulk = true;   // (nothing has been queried in the rebuilt grid: what follows is the bulk check's business)
+      HIPCHK(hipMemcpyAsync(w, g_ovfcnt.p, 8, hipMemcpyDeviceToHost, stream));
+      HIPCHK(hipStreamSynchronize(stream));
+    }
+  }
   HIPCHK(hipMemcpyAsync(&v, g_ovfcnt.p, 4, hipMemcpyDeviceToHost, stream));
   HIPCHK(hipStreamSynchronize(stream));
   if (bulk) {
@@ -1203,6 +1258,7 @@ void Ctx::rrt_chain(const double* rnd6, const int32_t* tree, int n, double dist,
   int32_t* r_nc = reinterpret_cast<int32_t*>(db + L1.o_nc);
   HIPCHK(hipMemcpyAsync(rr_q1.p, rr_hq.p, (size_t)n * sizeof(sffk::KnnQuery), hipMemcpyHostToDevice, stream));
   if ((by_grid1 || (kmax > 0 && by_gridk)) && grid_on) {
+    grid_dense();   // (k_knn_grid does not know the compact layout)
     grid_insert_new();
     grid_check(/*bulk=*/true);
   }
@@ -1450,6 +1506,7 @@ void Ctx::knn(const double* q6, int nq, int k, const int32_t* tree, const int32_
     // would make the shells grow over the whole grid) every query is answered from the cells around it
     const bool by_grid = grid_on && (tree == nullptr || tree_by_grid) && store_n >= k;
     if (by_grid) {
+      grid_dense();   // (k_knn_grid does not know the compact layout)
       grid_insert_new();
       grid_check(/*bulk=*/true);
     }
@@ -1525,3 +1582,8 @@ void Ctx::knn(const double* q6, int nq, int k, const int32_t* tree, const int32_
 }
 
 }  // namespace sff
+
+// kernels.h: the launchers of kernels that read a node grid without knowing the compact layout call this first
+void sffk::grid_dense_only(const GridView& g, const char* kernel) {
+  if (g.bucket) throw sff::HipError{std::string(kernel) + ": handed a compact node grid (Ctx::grid_dense() has to come first)"};
+}

@@ -172,6 +172,7 @@ struct Ctx {
   bool grid_on = false;
   sffk::GridView gridv{};
   DevBuf g_cnt, g_items, g_ovfcnt, g_ovf, g_lite, g_ovf_lite;
+  DevBuf g_bucket;   // the compact layout's per-cell table (its pool counter is the second word of g_ovfcnt)
   DevBuf t_cnt, t_items, t_ovfcnt, t_ovf, t_occ, t_lite, t_ovf_lite;   // the round's own grid (same cells; filled and emptied every round)
   sffk::GridView tgridv{};
   // A member context (sffgpu_create_member) carries of the round grid only the counter t_ovfcnt - tgridv has its geometry
@@ -179,6 +180,16 @@ struct Ctx {
   // allocates and zeroes it as grid_setup does for every other context; called on the host before anything that reads
   // tgridv is enqueued or captured (never inside a capture).  A re-celling keeps the state: lean stays lean.
   bool round_lazy = false;    // a member context
+  // The compact node grid (sffk::GridView::bucket): a state of the context, decided once - a member created under
+  // SFFGPU_COMPACT_GRID=1 - and kept here; later knob snapshots (forest and session creation re-read them all) do not
+  // change it.  grid_setup builds the layout the state asks for: per-cell tables, a pool of grid_pool buckets (the
+  // store's capacity: a node opens at most one bucket), the overflow list; no filter records and no round grid.  Only the
+  // one-slot loops and the insert kernels understand it: everything else that hands gridv to a kernel calls grid_dense()
+  // first, on the host, before the launch or capture (next to round_grid()), and the context stays dense afterwards.
+  bool grid_compact = false;
+  int grid_pool = 0;          // buckets of the pool behind gridv (compact only)
+  int grid_pool_next = 0;     // ... the next grid_setup has to provide at least (grid_check after the pool ran out)
+  void grid_dense();          // compact -> dense: state cleared, grid_setup at the current limits and cell, every node re-inserted, bulk check
   bool round_ready = false;   // the round grid's buffers stand behind tgridv
   void round_grid();
   int grid_inserted = 0;
@@ -455,6 +466,7 @@ struct Forest {
   uint64_t seq_words_per_wave() const;             // engine words budgeted per wave (pick + ThresholdMisses samples)
   void seq_note_launch(uint64_t waves_before);     // after dev_finish_wave: did the launch get anywhere (priority mode's word slack)
   sffk::SeqArgs seq_prepare(int batch);            // tops the ring up to there, builds the kernel's arguments
+  void grid_dense();   // Ctx::grid_dense() with the store's node count as the device engine left it; before whatever reads gridv outside the one-slot loops
   void seq_lists_fault();                          // SFFK_FAULT_LISTS came back: that wave on the host-replay engine, state back up
   bool spec_setup();                // the speculative kernel's scenario tree and buffers; false = k_seq_waves_batch runs the loop
   bool seq_suspended = false;

@@ -456,6 +456,7 @@ void Forest::round_begin() {
   HIPCHK(hipSetDevice(c.device));
   if (pending_round) throw HipError{"forest: round_begin called twice without round_commit"};
   if (dev.active) dev_to_host();   // the round protocol runs on the host path
+  grid_dense();                    // (a compact node grid: the round kernels read the dense layout and its filter records)
   c.round_grid();                  // (a member context has none until here: the samples of a round go through it)
   if (!in_wave) {
     if (terminated()) return;

@@ -1164,6 +1164,7 @@ void Forest::dev_enqueue_wave_kernels(bool sharded, size_t words) {
 void Forest::dev_enqueue_wave(int slot) {
   Ctx& c = *ctx;
   DevEngine& d = dev;
+  grid_dense();             // (a compact node grid ends here: the round kernels read the dense layout)
   c.round_grid();           // (a member context: the round grid comes with the first wave of rounds - here, ahead of the capture below)
   d.wr.wait_on(c.stream);   // the words this wave may read have to be resident
   // (SFFGPU_TEST_EXCHANGE_SELF: a one-rank forest packs, all-gathers and unpacks too - the collective on one GPU)
@@ -1314,6 +1315,7 @@ bool Forest::dev_wave_begin() {
   if (!dev.on) throw HipError{"forest: the device engine does not drive this forest"};
   HIPCHK(hipSetDevice(ctx->device));
   exchange_timer_drop();
+  grid_dense();
   ctx->round_grid();   // (a member context: before the caller's first dev_round_eval)
   if (!dev.active) dev_upload_state();
   const sffk::DevCtrl& k = dev.last;
@@ -1453,6 +1455,18 @@ sffk::SeqArgs Forest::seq_prepare(int batch) {
   return a;
 }
 
+// a compact node grid becomes the dense one (Ctx::grid_dense).  While the device engine drives the forest the context's node
+// count is the last status block's (dev_finish_wave sets it the same way before a re-celling); the stream is idle.
+void Forest::grid_dense() {
+  Ctx& c = *ctx;
+  if (!c.grid_compact) return;
+  if (dev.active) {
+    c.store_n = dev.last.n_nodes;
+    c.grid_inserted = dev.last.n_nodes;
+  }
+  c.grid_dense();
+}
+
 // a bounded device list ran over inside the loop: the faulted wave is finished on the host-replay engine (unbounded lists)
 // and the state goes back to the device
 void Forest::seq_lists_fault() {
@@ -1490,6 +1504,8 @@ void Forest::run_device_seq(int max_waves) {
       continue;
     }
     const int batch = seq_launch_waves(max_waves > 0 ? max_waves - (int)(k.waves - w0) : 0);
+    const bool spec = spec_setup();
+    if (spec) grid_dense();   // (k_spec_waves keeps its own copy of the cell loops: a compact node grid ends here, before the arguments are taken)
     sffk::SeqArgs a = seq_prepare(batch);
     d.wr.wait_on(c.stream);
     const char* trace_path = kn.seq_trace.empty() ? nullptr : kn.seq_trace.c_str();
@@ -1501,7 +1517,6 @@ void Forest::run_device_seq(int max_waves) {
       a.trace_cap = batch;
     }
     const uint64_t waves_before = k.waves;
-    const bool spec = spec_setup();
     if (spec) {
       sffk::SpecArgs sa{};
       sa.q = a;

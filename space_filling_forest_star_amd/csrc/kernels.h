@@ -64,7 +64,21 @@ struct GridView {
   GridItem32* ovf_lite;
   uint32_t* occ;      // optional occupancy bits (one per cell): the round's own grid is nearly empty, its 100 KB of
                       // bits stay in L2 and spare the queries 27 scattered count loads
+  // The COMPACT layout (a member context under SFFGPU_COMPACT_GRID=1, Ctx::grid_setup): bucket != nullptr.  Only a cell
+  // that holds a node has a bucket: bucket[cell] (-1 = none yet) names it in items, which then has pool_cap x bk entries;
+  // the first insert into a cell takes one from the pool (pool_cnt) and publishes it with a compare-and-swap - nobody
+  // ever waits for a publication; with the pool used up the item goes to the overflow list.  No filter records (lite,
+  // ovf_lite null).  Understood by grid_put, grid_ball_items and sq_knn only - the one-slot loops and the insert
+  // kernels; every other launcher refuses such a view (grid_dense_only).  nullptr: the bucket of a cell is the cell.
+  int32_t* bucket;
+  int32_t* pool_cnt;  // [0] buckets ever asked for (may exceed pool_cap: the host then grows the pool, Ctx::grid_check)
+  int pool_cap;
 };
+
+// The guard of every launcher whose kernel reads or writes a node grid and does not know the compact layout: throws
+// sff::HipError (engine.cpp) when g is compact - a call site that missed Ctx::grid_dense() fails loudly instead of reading
+// another cell's bucket.
+void grid_dense_only(const GridView& g, const char* kernel);
 
 // What k_query_block needs of a sample, written by the kernel that draws it (one thread per sample, lane-dense) instead
 // of being derived by a few lanes of every query workgroup: 32 words, read back with one coalesced load.

@@ -818,6 +818,7 @@ __global__ __launch_bounds__(256) void k_star_knn_wg(ResolveArgs A, GridView g, 
 }
 void launch_star_knn_wg(hipStream_t s, const ResolveArgs& a, const GridView& g, const GridView& tg, const NodeStoreView& st,
                         double cell_edge, double slack, int n_bound, int R0) {
+  grid_dense_only(g, "k_star_knn_wg");
   int blocks = n_bound < 2048 ? n_bound : 2048;   // (a workgroup per accepted sample; more than 2 048 of them loop)
   if (blocks < 1) blocks = 1;
   hipLaunchKernelGGL(k_star_knn_wg, dim3(blocks), dim3(256), 0, s, a, g, tg, st, cell_edge, slack, R0);
@@ -4068,7 +4069,13 @@ __device__ __attribute__((noinline)) void sq_knn(const GridView& g, const double
       cl[u] = 0; mm[u] = 0;
       if (j < 125) {
         const int x = cx + j % 5 - 2, y = cy + (j / 5) % 5 - 2, z = cz + j / 25 - 2;
-        if (x >= 0 && x < g.nx && y >= 0 && y < g.ny && z >= 0 && z < g.nz) { cl[u] = (z * g.ny + y) * g.nx + x; mm[u] = sq_i32(g.cnt + cl[u]); }
+        if (x >= 0 && x < g.nx && y >= 0 && y < g.ny && z >= 0 && z < g.nz) {
+          cl[u] = (z * g.ny + y) * g.nx + x; mm[u] = sq_i32(g.cnt + cl[u]);
+          if (g.bucket) {   // compact grid: cl = the cell's bucket, asked for together with the count; none = an empty cell
+            cl[u] = sq_i32(g.bucket + cl[u]);
+            if (cl[u] < 0) { cl[u] = 0; mm[u] = 0; }
+          }
+        }
       }
     }
     ++d_sh; ++d_cg;
@@ -4180,6 +4187,10 @@ __device__ __attribute__((noinline)) void sq_knn(const GridView& g, const double
           if (x >= 0 && x < g.nx && y >= 0 && y < g.ny && z >= 0 && z < g.nz) {
             cl[u] = (z * g.ny + y) * g.nx + x;
             mm[u] = sq_i32(g.cnt + cl[u]);
+            if (g.bucket) {
+              cl[u] = sq_i32(g.bucket + cl[u]);
+              if (cl[u] < 0) { cl[u] = 0; mm[u] = 0; }
+            }
           }
         }
       }
@@ -5413,6 +5424,7 @@ void launch_rrt_mates(hipStream_t s, const KnnQuery* q1, const double* near_d, i
 }
 
 void launch_spec_waves(hipStream_t s, const SpecArgs& a) {
+  grid_dense_only(a.q.g, "k_spec_waves");
   const size_t lds = collide_lds_bytes(a.q.rob.n_tri, 1);
   const unsigned grid = 1u + (unsigned)(a.n_sets * a.n_slots);
   if (a.q.optimize) {
@@ -5525,6 +5537,7 @@ void launch_knn_grid(hipStream_t s, const GridView& g, const GridView* tg, const
                      int kcap, int32_t* idx, double* dist, int32_t* cnt, int32_t* mate_idx, int32_t* mate_cnt, double cell,
                      double slack, int mate_cap, int n_store) {
   if (nq <= 0) return;
+  grid_dense_only(g, "k_knn_grid");
   GridView none{};
   if (!tg && !mate_idx && !mate_cnt && nq <= 2048) {   // (more queries than that fill the chip with a wavefront each)
     hipLaunchKernelGGL(k_knn_grid_wg, dim3(nq), dim3(256), 0, s, g, st, q, nq, kcap, idx, dist, cnt, cell, slack, n_store, 0);
@@ -5586,6 +5599,7 @@ bool query_block_mode(const sff::Knobs& kn, const GridView& g, const GridView* t
 bool launch_query_classify(hipStream_t s, const sff::Knobs& kn, const GridView& g, const GridView* tg, const NodeStoreView& st,
                            const SweepQuery* queries, const ClassifyArgs& a, const EnvView* env) {
   if (a.n <= 0) return false;
+  grid_dense_only(g, "k_query_classify / k_query_block");
   GridView none{};
   ClassifyArgs aa = a;
   // tests shrink the survivor list to drive the exact kernel's table-scan path

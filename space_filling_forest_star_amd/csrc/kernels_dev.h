@@ -19,8 +19,33 @@ __device__ __forceinline__ size_t grid_cell_of(const GridView& g, float x, float
             cz = grid_coord(z, g.oz, g.inv_cell, g.nz);
   return ((size_t)cz * g.ny + cy) * g.nx + cx;
 }
+// (the sq_* / wt_* accesses below, declared here for the compact layout's table)
+__device__ __forceinline__ int sq_i32(const int32_t* p);
+// The bucket of a cell for an INSERT (GridView, the compact layout): the one the table names, or - the cell's first insert -
+// one taken from the pool and published with a compare-and-swap; whoever loses that race uses the winner's bucket and
+// leaves its own unused (a node opens at most one bucket, so a pool as large as the store never runs out).  Nobody
+// waits for anybody.  -1: the pool is used up and the cell still has none - the item belongs on the overflow list.
+__device__ __forceinline__ int grid_bucket_open(const GridView& g, size_t cell) {
+  int b = sq_i32(g.bucket + cell);
+  if (b >= 0) return b;
+  const int mine = atomicAdd(g.pool_cnt, 1);
+  if (mine >= g.pool_cap) return atomicCAS(g.bucket + cell, -1, -1);   // (what another insert may have published meanwhile)
+  const int was = atomicCAS(g.bucket + cell, -1, mine);
+  return was < 0 ? mine : was;
+}
 __device__ __forceinline__ void grid_put(const GridView& g, const GridItem& it) {
   const size_t cell = grid_cell_of(g, (float)it.p[0], (float)it.p[1], (float)it.p[2]);
+  if (g.bucket) {   // compact (wave-uniform: g is the launch's argument): fp64 items only, buckets from the pool
+    const int b = grid_bucket_open(g, cell);
+    const int slot = b >= 0 ? atomicAdd(g.cnt + cell, 1) : g.bk;   // (a cell without a bucket counts as empty: cnt stays)
+    if (slot < g.bk) {
+      g.items[(size_t)b * g.bk + slot] = it;
+    } else {
+      const int o = atomicAdd(g.ovf_cnt, 1);
+      if (o < g.ovf_cap) g.ovf[o] = it;   // the host checks ovf_cnt against ovf_cap
+    }
+    return;
+  }
   const int slot = atomicAdd(g.cnt + cell, 1);
   if (g.occ) atomicOr(g.occ + (cell >> 5), 1u << (cell & 31));
   GridItem32 lt;
@@ -92,11 +117,15 @@ __device__ __forceinline__ void grid_ball_items(const GridView& g, const double*
   const int total = wx * wy * wz;
   for (int c0 = 0; c0 < total; c0 += 64) {
     const int ci = c0 + lane;
-    int cell = 0, m = 0;
+    int cell = 0, m = 0;   // cell: from here on the cell's BUCKET (dense: the cell itself)
     if (ci < total) {
       const int q1 = ci / wx, q2 = q1 / wy;
       cell = ((lz + q2) * g.ny + (ly + q1 - q2 * wy)) * g.nx + (lx + ci - q1 * wx);
       m = sq_i32(g.cnt + cell);
+      if (g.bucket) {   // compact: the table's word asked for together with the count (same address pattern, independent)
+        cell = sq_i32(g.bucket + cell);
+        if (cell < 0) { cell = 0; m = 0; }
+      }
       if (m > g.bk) m = g.bk;
     }
     int inc = m;

@@ -44,6 +44,8 @@ Knobs Knobs::from_env() {
   k.test_grid_bk = int_in("SFFGPU_TEST_GRID_BK", k.test_grid_bk, 1, 8);
   k.test_grid_bkmax = int_in("SFFGPU_TEST_GRID_BKMAX", k.test_grid_bkmax, 1, 64);
   k.test_grid_ovf = int_in("SFFGPU_TEST_GRID_OVF", k.test_grid_ovf);
+  k.compact_grid = flag("SFFGPU_COMPACT_GRID", k.compact_grid);
+  k.test_grid_pool = int_in("SFFGPU_TEST_GRID_POOL", k.test_grid_pool, 1, 1 << 26);
 
   k.query = is("SFFGPU_QUERY", "wide") ? QUERY_WIDE : is("SFFGPU_QUERY", "block") ? QUERY_BLOCK : QUERY_AUTO;
   k.share = is_set("SFFGPU_SHARE") ? (flag("SFFGPU_SHARE", false) ? 1 : 0) : -1;

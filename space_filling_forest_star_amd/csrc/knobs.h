@@ -28,6 +28,9 @@ struct Knobs {
   int test_grid_bk = 8;             // SFFGPU_TEST_GRID_BK (1..8), tests: tiny buckets to start with
   int test_grid_bkmax = 64;         // SFFGPU_TEST_GRID_BKMAX (1..64), tests: shallow buckets
   int test_grid_ovf = -1;           // SFFGPU_TEST_GRID_OVF, tests: tiny overflow list (raw value, < 0 = unset; Ctx::grid_setup scales it)
+  bool compact_grid = false;        // SFFGPU_COMPACT_GRID=1: a member context (sffgpu_create_member) created under it starts with the compact node grid
+                                    // (sffk::GridView::bucket: buckets from a pool sized by the node store); sffgpu_create contexts never do
+  int test_grid_pool = 0;           // SFFGPU_TEST_GRID_POOL=n (>= 1), tests: first pool capacity of a compact grid (0 = unset: the store's capacity)
 
   // ---- launch shapes (kernels.hip / devstar.hip)
   Query query = QUERY_AUTO;         // SFFGPU_QUERY=wide / block: force k_query_classify / k_query_block
