@@ -21,6 +21,7 @@
 #include "sff_geom.h"
 #include "kernels_dev.h"
 #include "star_pass_dev.h"
+#include "knn_dev.h"
 #include <cmath>
 #include <cstring>
 #include <cstdlib>
@@ -35,22 +36,14 @@ using namespace sffg;
 // permanent nodes (id < N0) of the sample's tree
 __device__ __forceinline__ void star_cells(const GridView& g, int m, int cell, int lane, const double* qp, int tree, int N0,
                                            TopK& t, int k, int& have) {
-  int inc = m;
-  for (int off = 1; off < 64; off <<= 1) {
-    const int o = __shfl_up(inc, off);
-    if (lane >= off) inc += o;
-  }
+  const int inc = lane_scan_incl(m, lane);
   const int total = __shfl(inc, 63);
   for (int base = 0; base < total; base += 64) {
     const int j = base + lane;
     const int jj = j < total ? j : total - 1;
-    int lo = 0, hi = 63;
-    while (lo < hi) {
-      const int mid = (lo + hi) >> 1;
-      if (__shfl(inc, mid) > jj) hi = mid; else lo = mid + 1;
-    }
+    const int lo = lane_owner(inc, jj);
     const int src_cell = __shfl(cell, lo);
-    const int slot = jj - (__shfl(inc, lo) - __shfl(m, lo));
+    const int slot = lane_slot(inc, m, jj, lo);
     bool cand = false;
     double d = 1.0e300;
     int id = 0x7fffffff;
@@ -70,7 +63,6 @@ __device__ __forceinline__ void star_cells(const GridView& g, int m, int cell, i
 // two sampling distances whatever the grid's cell size has become (the grid re-cells itself as the forest gets denser)
 #define STAR_R0_MAX 4
 #define STAR_U (((2 * STAR_R0_MAX + 1) * (2 * STAR_R0_MAX + 1) * (2 * STAR_R0_MAX + 1) + 63) / 64)
-#define STAR_MATE_U 16                              // x 64 accepted samples of a round whose list is scanned from registers
 #define STAR_POOL 10                                // batches of 64 cube candidates selected from at once
 #define STAR_INF_BITS 0x7ff0000000000000ULL
 __global__ __launch_bounds__(256) void k_star_knn(ResolveArgs A, GridView g, GridView tg, NodeStoreView st, double cell_edge,
@@ -82,9 +74,7 @@ __global__ __launch_bounds__(256) void k_star_knn(ResolveArgs A, GridView g, Gri
   const StarView& S = A.S;
   const DevCtrl* c = f.ctrl;
   const int n = c->app_n;
-  if (blockIdx.x == 0 && threadIdx.x < SFFK_STAR_PASSES) S.changed[threadIdx.x] = 0;
-  if (blockIdx.x == 0 && threadIdx.x == 0) { S.changed[SFFK_STAR_BAR] = 0; S.hdr[STAR_PASSES_RUN] = 0; S.hdr[STAR_CONVERGED] = 0; }   // (k_star_tail)
-  for (int t = blockIdx.x * 256 + threadIdx.x; t < SFFK_STAR_PASSES * SFFK_SUBLISTS * SFFK_STAR_SUB; t += gridDim.x * 256) S.sub[t] = 0;
+  star_launch_reset(S);
   if (n <= 0) return;
   const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
   const int i = blockIdx.x * 4 + wave;
@@ -96,9 +86,7 @@ __global__ __launch_bounds__(256) void k_star_knn(ResolveArgs A, GridView g, Gri
   const unsigned long long dbg_t0 = S.dbg ? wall_clock64() : 0ULL;
   unsigned long long dbg_t1 = 0, dbg_t2 = 0, dbg_t3 = 0, dbg_c1 = 0, dbg_c2 = 0, dbg_c3 = 0;
   int dbg_shells = 0, dbg_total = 0;
-  // k = (size_t)(2e log10(#nodes)) with the nodes accepted before this sample counted in (src/forest.h:309)
-  const int Nn = N0 + r;
-  const int k_ref = __popcll(__ballot(lane > 0 && lane <= SFFK_STAR_KMAX + 1 && S.ktab[lane] <= Nn));
+  const int k_ref = star_k(S, N0 + r, lane);
   const int self = Tb + i;
   const int mine = st.tree[self];
   double qp[6];
@@ -107,9 +95,7 @@ __global__ __launch_bounds__(256) void k_star_knn(ResolveArgs A, GridView g, Gri
   // of the round (rank -> sample -> tree: two dependent trips that used to follow the cube and the shells, 12.5 us per
   // sample) and lane 0's first guess (expanded node -> its cost)
   int sidv[STAR_MATE_U];
-  const bool mates_small = r > 0 && r <= 64 * STAR_MATE_U;
-#pragma unroll
-  for (int u = 0; u < STAR_MATE_U; ++u) { const int rq = 64 * u + lane; sidv[u] = (mates_small && rq < r) ? Tb + S.acc_sample[rq] : -1; }
+  star_earlier_ids(S, Tb, r, lane, true, sidv);
   const int ex0 = A.parent[i];
   const double pd0 = A.pdist[i];
   const int no_raw = g.ovf_cnt[0];
@@ -143,18 +129,15 @@ __global__ __launch_bounds__(256) void k_star_knn(ResolveArgs A, GridView g, Gri
     for (int u = 0; u < STAR_U; ++u) {
       const int cc = u * 64 + lane;
       cellv[u] = 0; mv[u] = 0;
-      if (cc < cube) {
-        const int x = cx + cc % W5 - R0, y = cy + (cc / W5) % W5 - R0, z = cz + cc / (W5 * W5) - R0;
-        if (x >= 0 && x < g.nx && y >= 0 && y < g.ny && z >= 0 && z < g.nz) {
-          cellv[u] = (z * g.ny + y) * g.nx + x;
-          mv[u] = g.cnt[cellv[u]];
-        }
+      if (cc < cube) {   // (the counts are clamped to the bucket size below, once the other loads are out)
+        int x, y, z;
+        cube_cell(cx, cy, cz, R0, cc, x, y, z);
+        if (grid_cell_in(g, x, y, z, cellv[u])) mv[u] = g.cnt[cellv[u]];
       }
     }
     // (the second trips of the loads asked for at the top go out while the cube's counts are on their way; so do the first
     // 128 entries of the node grid's shared overflow list, which every sample scans after its cube)
-#pragma unroll
-    for (int u = 0; u < STAR_MATE_U; ++u) trv[u] = sidv[u] >= 0 ? st.tree[sidv[u]] : -1;
+    star_earlier_trees(st, sidv, trv);
     dr0 = f.d_root[ex0];
     const int no_pre = no_raw < g.ovf_cap ? no_raw : g.ovf_cap;
 #pragma unroll
@@ -168,11 +151,7 @@ __global__ __launch_bounds__(256) void k_star_knn(ResolveArgs A, GridView g, Gri
       int mine_sum = 0;
 #pragma unroll
       for (int u = 0; u < STAR_U; ++u) mine_sum += mv[u];
-      int inc = mine_sum;
-      for (int off = 1; off < 64; off <<= 1) {
-        const int o = __shfl_up(inc, off);
-        if (lane >= off) inc += o;
-      }
+      const int inc = lane_scan_incl(mine_sum, lane);
       const int total = __shfl(inc, 63);
       dbg_total = total;
       if (S.dbg) dbg_c1 = wall_clock64();
@@ -182,12 +161,8 @@ __global__ __launch_bounds__(256) void k_star_knn(ResolveArgs A, GridView g, Gri
         for (int h = 0; h < 2; ++h) {
           const int j = base + 64 * h + lane;
           const int jj = j < total ? j : total - 1;
-          int lo = 0, hi = 63;
-          while (lo < hi) {
-            const int mid = (lo + hi) >> 1;
-            if (__shfl(inc, mid) > jj) hi = mid; else lo = mid + 1;
-          }
-          int rest = jj - (__shfl(inc, lo) - __shfl(mine_sum, lo));   // index among the owner lane's items
+          const int lo = lane_owner(inc, jj);
+          int rest = lane_slot(inc, mine_sum, jj, lo);   // index among the owner lane's items
           int src_cell = 0;
 #pragma unroll
           for (int u = 0; u < STAR_U; ++u) {
@@ -334,25 +309,13 @@ __global__ __launch_bounds__(256) void k_star_knn(ResolveArgs A, GridView g, Gri
         }
       }
     }
-    {   // the node grid's shared overflow list (usually empty)
-      int no = no_raw;
-      if (no > g.ovf_cap) no = g.ovf_cap;
-      for (int base = 0; base < no; base += 64) {
-        const int j = base + lane;
-        bool cand = false;
-        double d = 1.0e300;
-        int id = 0x7fffffff;
-        const double worst = topk_worst(t, k, have);
-        if (j < no) {
-          const GridItem it = base == 0 ? ovf_pre[0] : (base == 64 ? ovf_pre[1] : g.ovf[j]);
-          id = it.id;
-          if (id < N0 && it.tree == mine) {
-            d = dist6(it.p, qp);
-            cand = have < k || key_less(d, id, worst, 0x7fffffff);
-          }
-        }
-        topk_insert(t, lane, k, have, __ballot(cand), d, id);
-      }
+    // the node grid's shared overflow list: its first two batches are here already
+    {
+      const auto store_node = [&](int id, int tree) { return id < N0 && tree == mine; };
+#pragma unroll
+      for (int h = 0; h < 2; ++h)
+        if (64 * h < no_pre) have = ovf_batch(64 * h + lane < no_pre, &ovf_pre[h], lane, qp, t, k, have, store_node);
+      have = ovf_scan_n(g.ovf, no_pre, 128, 64, lane, qp, t, k, have, store_node);
     }
     // ---- beyond the cube (rare: young, sparse trees): shells of cells until the k-th distance lies inside the covered
     // ball; a tree with fewer than k nodes is complete as soon as all of them are in
@@ -365,9 +328,8 @@ __global__ __launch_bounds__(256) void k_star_knn(ResolveArgs A, GridView g, Gri
         // only the shell's own cells (two caps of w x w, w - 2 rings of 8 rr: 24 rr^2 + 2 of the cube's (2 rr + 1)^3 - the
         // loop used to run over the whole cube and mask its inside), four cells per lane and trip so that the counts of
         // 256 cells are on their way together (round 5, like k_knn_grid)
-        const int w = 2 * rr + 1;
-        const int ww = w * w, ring = 8 * rr;
-        const int total = 2 * ww + (w - 2) * ring;
+        const Shell sh = shell_of(rr);
+        const int total = sh.cells;
         for (int c0 = 0; c0 < total; c0 += 256) {
           int cellq[4], mq[4];
 #pragma unroll
@@ -376,23 +338,8 @@ __global__ __launch_bounds__(256) void k_star_knn(ResolveArgs A, GridView g, Gri
             cellq[u] = 0; mq[u] = 0;
             if (cq < total) {
               int ox, oy, oz;
-              if (cq < 2 * ww) {
-                const int face = cq >= ww ? 1 : 0, ii = cq - face * ww;
-                ox = ii % w - rr; oy = ii / w - rr; oz = face ? rr : -rr;
-              } else {
-                const int cc = cq - 2 * ww;
-                const int layer = cc / ring, pp = cc - layer * ring;
-                const int side = pp / (2 * rr), t_ = pp - side * 2 * rr;
-                oz = -rr + 1 + layer;
-                ox = side == 0 ? -rr + t_ : side == 1 ? rr : side == 2 ? rr - t_ : -rr;
-                oy = side == 0 ? -rr : side == 1 ? -rr + t_ : side == 2 ? rr : rr - t_;
-              }
-              const int x = cx + ox, y = cy + oy, z = cz + oz;
-              if (x >= 0 && x < g.nx && y >= 0 && y < g.ny && z >= 0 && z < g.nz) {
-                cellq[u] = (z * g.ny + y) * g.nx + x;
-                mq[u] = g.cnt[cellq[u]];
-                if (mq[u] > g.bk) mq[u] = g.bk;
-              }
+              shell_cell(sh, cq, ox, oy, oz);
+              grid_cell_fill(g, g, cx + ox, cy + oy, cz + oz, cellq[u], mq[u]);
             }
           }
 #pragma unroll
@@ -400,139 +347,23 @@ __global__ __launch_bounds__(256) void k_star_knn(ResolveArgs A, GridView g, Gri
             if (__any(mq[u] > 0)) star_cells(g, mq[u], cellq[u], lane, qp, mine, N0, t, k, have);
         }
       }
-      const double covered = (double)rr * cell_edge - slack;
+      const double covered = shells_reach(rr, cell_edge, slack);
       if (have >= k && topk_worst(t, k, have) <= covered) break;
-      if (cx - rr <= 0 && cy - rr <= 0 && cz - rr <= 0 && cx + rr >= g.nx - 1 && cy + rr >= g.ny - 1 && cz + rr >= g.nz - 1) break;
+      if (shells_cover_grid(g, cx, cy, cz, rr)) break;
     }
-    // ---- the samples accepted earlier in this round (ranks below this one's, k_commit's list) of the same tree: not
-    // farther than the k-th store node - or, while the store holds fewer than k nodes of the tree, all of them
     if (S.dbg) dbg_t2 = wall_clock64();
-    if (r > 0) {
-      const bool all = have < k;
-      const double limit = all ? 1.0e300 : topk_worst(t, k, have);
-      if (r <= 64 * STAR_MATE_U) {
-        // k_commit's list of the accepted samples: every rank's sample and tree are requested up front (two trips to
-        // memory whatever the length), the few of the same tree are compacted in LDS and measured a batch at a time
-        int* ml = s_mate[wave];
-        int nm = 0;
-#pragma unroll
-        for (int u = 0; u < STAR_MATE_U; ++u) {
-          if (64 * u >= r) break;
-          const bool mt = sidv[u] >= 0 && trv[u] == mine;
-          const unsigned long long mm = __ballot(mt);
-          if (mt) ml[nm + __popcll(mm & ((1ULL << lane) - 1ULL))] = sidv[u];
-          nm += __popcll(mm);
-        }
-        __builtin_amdgcn_wave_barrier();
-        for (int base = 0; base < nm; base += 64) {
-          const int j = base + lane;
-          bool cand = false;
-          double d = 1.0e300;
-          int sid = 0x7fffffff;
-          if (j < nm) {
-            sid = ml[j];
-            double mp[6];
-            for (int q = 0; q < 6; ++q) mp[q] = st.pos[6 * (size_t)sid + q];
-            d = dist6(mp, qp);
-            cand = d <= limit;
-          }
-          const double worst = topk_worst(t, k, have);
-          cand = cand && (have < k || key_less(d, sid, worst, 0x7fffffff));
-          topk_insert(t, lane, k, have, __ballot(cand), d, sid);
-        }
-      } else if (all) {
-        for (int base = 0; base < r; base += 64) {   // (a tree wanted whole in a huge round: rare)
-          const int rq = base + lane;
-          bool cand = false;
-          double d = 1.0e300;
-          int sid = 0x7fffffff;
-          if (rq < r) {
-            sid = Tb + S.acc_sample[rq];
-            if (st.tree[sid] == mine) {
-              double mp[6];
-              for (int q = 0; q < 6; ++q) mp[q] = st.pos[6 * (size_t)sid + q];
-              d = dist6(mp, qp);
-              cand = true;
-            }
-          }
-          const double worst = topk_worst(t, k, have);
-          cand = cand && (have < k || key_less(d, sid, worst, 0x7fffffff));
-          topk_insert(t, lane, k, have, __ballot(cand), d, sid);
-        }
-      } else {
-        // a large round: the round's own grid, cells of the cube around the ball of the k-th store node
-        int rr = (int)((limit + slack) / cell_edge) + 1;
-        if (rr > rmax) rr = rmax;
-        const int w = 2 * rr + 1;
-        const int total = w * w * w;
-        for (int c0 = 0; c0 < total; c0 += 64) {
-          const int cc = c0 + lane;
-          int cell = 0, m = 0;
-          if (cc < total) {
-            const int x = cx + cc % w - rr, y = cy + (cc / w) % w - rr, z = cz + cc / (w * w) - rr;
-            if (x >= 0 && x < g.nx && y >= 0 && y < g.ny && z >= 0 && z < g.nz) {
-              cell = (z * g.ny + y) * g.nx + x;
-              const bool maybe = tg.occ ? ((tg.occ[cell >> 5] >> (cell & 31)) & 1u) != 0 : true;
-              if (maybe) { m = tg.cnt[cell]; if (m > tg.bk) m = tg.bk; }
-            }
-          }
-          if (__any(m > 0)) star_cells_mates(tg, m, cell, lane, qp, mine, Tb, self, limit, f, t, k, have);
-        }
-        int no = tg.ovf_cnt[0];
-        if (no > tg.ovf_cap) no = tg.ovf_cap;
-        for (int base = 0; base < no; base += 64) {
-          const int j = base + lane;
-          bool cand = false;
-          double d = 1.0e300;
-          int id = 0x7fffffff;
-          const double worst = topk_worst(t, k, have);
-          if (j < no) {
-            const GridItem it = tg.ovf[j];
-            id = it.id;
-            int rk;
-            if (it.tree == mine && id >= Tb && id < self && star_accepted(f, id - Tb, rk)) {
-              d = dist6(it.p, qp);
-              cand = d <= limit && (have < k || key_less(d, id, worst, 0x7fffffff));
-            }
-          }
-          topk_insert(t, lane, k, have, __ballot(cand), d, id);
-        }
-      }
-    }
+    star_earlier_samples(S, f, g, tg, st, qp, mine, Tb, self, r, sidv, trv, s_mate[wave], cx, cy, cz, rmax, cell_edge, slack, lane, t, k, have);
   }
   if (S.dbg) dbg_t3 = wall_clock64();
-  // ---- the members: ids, distances, toucher lists
-  const int cnt = have;
-  const bool mem = lane < cnt;
-  int node = -1;
-  if (mem) {
-    if (t.id < N0) node = t.id;
-    else { int rk; star_accepted(f, t.id - Tb, rk); node = N0 + rk; }
-  }
-  const size_t p = (size_t)i * SFFK_STAR_KC + lane;
-  S.prop[p] = STAR_INF;
-  if (mem) {
-    S.m_id[p] = node;
-    S.m_d[p] = t.d;
-    const unsigned long long mark = ((unsigned long long)ep << 32) | (unsigned long long)(p + 1);
-    const unsigned long long old = atomicExch(&S.head[node], mark);
-    S.next[p] = (unsigned)(old >> 32) == ep ? (int)(unsigned)(old & 0xffffffffULL) : 0;
-  }
-  if (lane == 0) {
-    S.m_cnt[i] = cnt;
-    S.best[i] = pd0 + dr0;   // (first guess: the plain SFF cost)
-    S.psel[i] = ex0;
-    S.dcl[i] = pd0;
-    S.cnt[2 * (size_t)i] = 0ULL; S.cnt[2 * (size_t)i + 1] = 0ULL;
-    if (S.dbg && k > 0) {   // waves | ticks: cube, shells, mates, lists | shells walked | cube candidates | longest wave
-      const unsigned long long t4 = wall_clock64();
-      atomicAdd(S.dbg + 0, 1ULL); atomicAdd(S.dbg + 1, dbg_t1 - dbg_t0); atomicAdd(S.dbg + 2, dbg_t2 - dbg_t1);
-      atomicAdd(S.dbg + 3, dbg_t3 - dbg_t2); atomicAdd(S.dbg + 4, t4 - dbg_t3); atomicAdd(S.dbg + 5, (unsigned long long)dbg_shells);
-      atomicAdd(S.dbg + 6, (unsigned long long)dbg_total); atomicMax(S.dbg + 7, t4 - dbg_t0);
-      if (dbg_shells) atomicAdd(S.dbg + 8, 1ULL);
-      atomicAdd(S.dbg + 9, dbg_c1 - dbg_t0); atomicAdd(S.dbg + 10, dbg_c2 - dbg_c1); atomicAdd(S.dbg + 11, dbg_c3 - dbg_c2);
-      atomicAdd(S.dbg + 12, dbg_t1 - dbg_c3);
-    }
+  star_publish(S, f, i, N0, Tb, ep, lane, t, have, ex0, pd0, dr0);
+  if (lane == 0 && S.dbg && k > 0) {   // waves | ticks: cube, shells, mates, lists | shells walked | cube candidates | longest wave
+    const unsigned long long t4 = wall_clock64();
+    atomicAdd(S.dbg + 0, 1ULL); atomicAdd(S.dbg + 1, dbg_t1 - dbg_t0); atomicAdd(S.dbg + 2, dbg_t2 - dbg_t1);
+    atomicAdd(S.dbg + 3, dbg_t3 - dbg_t2); atomicAdd(S.dbg + 4, t4 - dbg_t3); atomicAdd(S.dbg + 5, (unsigned long long)dbg_shells);
+    atomicAdd(S.dbg + 6, (unsigned long long)dbg_total); atomicMax(S.dbg + 7, t4 - dbg_t0);
+    if (dbg_shells) atomicAdd(S.dbg + 8, 1ULL);
+    atomicAdd(S.dbg + 9, dbg_c1 - dbg_t0); atomicAdd(S.dbg + 10, dbg_c2 - dbg_c1); atomicAdd(S.dbg + 11, dbg_c3 - dbg_c2);
+    atomicAdd(S.dbg + 12, dbg_t1 - dbg_c3);
   }
 }
 

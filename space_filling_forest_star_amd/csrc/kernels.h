@@ -559,8 +559,9 @@ struct DevForestView {
 //   k_star_knn(_wg) one wavefront (_wg: one workgroup, kernels.hip) per accepted sample: its k = floor(2e log10(#nodes at its turn)) nearest nodes of its
 //                 tree among the store AND the samples accepted earlier in the round (replaces knnSearch, :317); every
 //                 member joins the toucher list of its node (per-node linked lists, heads stamped with the round's
-//                 epoch: no clearing)
-//   k_star_pass   the sequential semantics "sample i sees the rewires of every accepted sample before it" as a fixed
+//                 epoch: no clearing).  The two kernels differ in the store search only; what follows it - the earlier
+//                 samples, the members and their toucher lists - is one text for both (knn_dev.h)
+//   k_star_pass  the sequential semantics "sample i sees the rewires of every accepted sample before it" as a fixed
 //                 point: a sample's view of a member's DistanceToRoot = the proposal of the LATEST earlier sample that
 //                 rewires that node (walk of the node's toucher list), else the node's stored cost; from its views it
 //                 recomputes its parent / cost / rewire proposals.  Dependencies only point backwards in slot order, so
@@ -820,7 +821,8 @@ struct SampleLaunch {
   RoundTemps tmp; DevRound dv;
 };
 // SFF*: the k nearest of every accepted sample, one workgroup per sample (k_star_knn_wg in kernels.hip; devstar.hip's
-// k_star_knn - one wavefront per sample - remains behind SFFGPU_STAR_KNN=lone)
+// k_star_knn - one wavefront per sample - remains behind SFFGPU_STAR_KNN=lone; the stages behind the store search are
+// knn_dev.h's, shared by the two)
 void launch_star_knn_wg(hipStream_t s, const ResolveArgs& a, const GridView& g, const GridView& tg, const NodeStoreView& st,
                         double cell_edge, double slack, int n_bound, int R0);
 void launch_commit(hipStream_t s, const ResolveArgs& a, int n_bound, const StarLaunch* star = nullptr,

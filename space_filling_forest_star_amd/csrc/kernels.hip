@@ -25,6 +25,7 @@
 #include "sff_geom.h"
 #include "kernels_dev.h"
 #include "star_pass_dev.h"
+#include "knn_dev.h"
 #include "prio_heap_dev.h"
 
 namespace sffk {
@@ -169,16 +170,12 @@ __global__ __launch_bounds__(256) void k_knn_linear(NodeStoreView st, int n_stor
 __device__ __forceinline__ void knn_cells(const GridView& g, int m, int cell, int lane, const KnnQuery& Q, const NodeStoreView& st,
                                           TopK& t, int k, int& have, bool mates, double mate_limit, int32_t* mate_out, int& n_mates, int mate_cap,
                                           double bound_d = 1.0e300, int bound_id = 0x7fffffff) {
-  int inc = m;
-  for (int off = 1; off < 64; off <<= 1) {
-    const int o = __shfl_up(inc, off);
-    if (lane >= off) inc += o;
-  }
+  const int inc = lane_scan_incl(m, lane);
   const int total = __shfl(inc, 63);
   for (int base = 0; base < total; base += 64) {
     const int j = base + lane;
     const int jj = j < total ? j : total - 1;
-    int lo = 0, hi = 63;
+    int lo = 0, hi = 63;   // (lane_owner / lane_slot of knn_dev.h, spelled out: through the helpers k_knn_grid_wg's stream changes)
     while (lo < hi) {
       const int mid = (lo + hi) >> 1;
       if (__shfl(inc, mid) > jj) hi = mid; else lo = mid + 1;
@@ -226,27 +223,9 @@ __global__ __launch_bounds__(256) void k_knn_grid(GridView g, GridView tg, NodeS
   int have = 0, n_mates = 0;
   const int cx = grid_coord((float)Q.pos[0], g.ox, g.inv_cell, g.nx), cy = grid_coord((float)Q.pos[1], g.oy, g.inv_cell, g.ny),
             cz = grid_coord((float)Q.pos[2], g.oz, g.inv_cell, g.nz);
-  // shared overflow list first (usually empty)
-  {
-    int no = g.ovf_cnt[0];
-    if (no > g.ovf_cap) no = g.ovf_cap;
-    for (int base = 0; base < no; base += 64) {
-      const int j = base + lane;
-      bool cand = false;
-      double d = 1.0e300;
-      int id = 0x7fffffff;
-      const double worst = topk_worst(t, k, have);   // (a shuffle: outside the divergent code below)
-      if (j < no) {
-        const GridItem it = g.ovf[j];
-        id = it.id;
-        if (id < Q.max_id && id < Q.mate_base && (Q.tree < 0 || it.tree == Q.tree)) {
-          d = dist6(it.p, Q.pos);
-          cand = have < k || key_less(d, id, worst, 0x7fffffff);
-        }
-      }
-      topk_insert(t, lane, k, have, __ballot(cand), d, id);
-    }
-  }
+  // shared overflow list first
+  have = ovf_scan(g, 0, 64, lane, Q.pos, t, k, have,
+           [&](int id, int tree) { return id < Q.max_id && id < Q.mate_base && (Q.tree < 0 || tree == Q.tree); });
   // shells of cells around the query's cell: shell r = the cube of half-width r minus the cube of half-width r-1.
   // After shell r every node within r * cell_edge (minus fp32 slack) of the query has been seen.  Only the shell's own
   // cells are enumerated (two caps of w x w cells, w - 2 rings of 8 r in between; until round 4 the loop ran over the
@@ -258,9 +237,8 @@ __global__ __launch_bounds__(256) void k_knn_grid(GridView g, GridView tg, NodeS
   long long scanned = 0;
   bool sweep = false;
   for (int r = 0; r <= rmax; ++r) {
-    const int w = 2 * r + 1;
-    const int ww = w * w, ring = 8 * r;
-    const int total = r > 0 ? 2 * ww + (w - 2) * ring : 1;
+    const Shell sh = shell_of(r);
+    const int total = r > 0 ? sh.cells : 1;
     if (n_store > 0 && scanned + total > 4LL * n_store + 4096) { sweep = true; break; }
     scanned += total;
     for (int c0 = 0; c0 < total; c0 += 256) {
@@ -271,32 +249,17 @@ __global__ __launch_bounds__(256) void k_knn_grid(GridView g, GridView tg, NodeS
         cell[u] = 0; m[u] = 0;
         if (c < total) {
           int ox, oy, oz;
-          if (c < 2 * ww) {
-            const int face = c >= ww ? 1 : 0, i = c - face * ww;
-            ox = i % w - r; oy = i / w - r; oz = face ? r : -r;
-          } else {
-            const int cc = c - 2 * ww;
-            const int layer = cc / ring, pp = cc - layer * ring;
-            const int side = pp / (2 * r), t_ = pp - side * 2 * r;
-            oz = -r + 1 + layer;
-            ox = side == 0 ? -r + t_ : side == 1 ? r : side == 2 ? r - t_ : -r;
-            oy = side == 0 ? -r : side == 1 ? -r + t_ : side == 2 ? r : r - t_;
-          }
-          const int x = cx + ox, y = cy + oy, z = cz + oz;
-          if (x >= 0 && x < g.nx && y >= 0 && y < g.ny && z >= 0 && z < g.nz) {
-            cell[u] = (z * g.ny + y) * g.nx + x;
-            m[u] = g.cnt[cell[u]];
-            if (m[u] > g.bk) m[u] = g.bk;
-          }
+          shell_cell(sh, c, ox, oy, oz);
+          grid_cell_fill(g, g, cx + ox, cy + oy, cz + oz, cell[u], m[u]);
         }
       }
 #pragma unroll
       for (int u = 0; u < 4; ++u)
         if (__any(m[u] > 0)) knn_cells(g, m[u], cell[u], lane, Q, st, t, k, have, false, 0.0, nullptr, n_mates, 0);
     }
-    const double covered = (double)r * cell_edge - slack;   // (cells are assigned from fp32 coordinates)
+    const double covered = shells_reach(r, cell_edge, slack);
     if (have >= k && topk_worst(t, k, have) <= covered) break;
-    if (cx - r <= 0 && cy - r <= 0 && cz - r <= 0 && cx + r >= g.nx - 1 && cy + r >= g.ny - 1 && cz + r >= g.nz - 1) break;
+    if (shells_cover_grid(g, cx, cy, cz, r)) break;
   }
   if (sweep) {   // (k_knn_linear's loop; what the shells found is found again)
     t = TopK{1.0e300, 0x7fffffff};
@@ -359,12 +322,9 @@ __global__ __launch_bounds__(256) void k_knn_grid(GridView g, GridView tg, NodeS
         const int c = c0 + lane;
         int cell = 0, m = 0;
         if (c < total) {
-          const int x = cx + c % w - rr, y = cy + (c / w) % w - rr, z = cz + c / (w * w) - rr;
-          if (x >= 0 && x < g.nx && y >= 0 && y < g.ny && z >= 0 && z < g.nz) {
-            cell = (z * g.ny + y) * g.nx + x;
-            const bool maybe = tg.occ ? ((tg.occ[cell >> 5] >> (cell & 31)) & 1u) != 0 : true;
-            if (maybe) { m = tg.cnt[cell]; if (m > tg.bk) m = tg.bk; }
-          }
+          int x, y, z;
+          cube_cell(cx, cy, cz, rr, c, x, y, z);
+          grid_cell_fill<true>(g, tg, x, y, z, cell, m);
         }
         if (__any(m > 0)) knn_cells(tg, m, cell, lane, Q, st, t, k, have, true, limit, mate_idx + (size_t)q * mate_cap, n_mates, mate_cap);
       }
@@ -451,7 +411,8 @@ __device__ void knn_wg_search(const GridView& g, const NodeStoreView& st, const 
   };
   const int cx = grid_coord((float)Q.pos[0], g.ox, g.inv_cell, g.nx), cy = grid_coord((float)Q.pos[1], g.oy, g.inv_cell, g.ny),
             cz = grid_coord((float)Q.pos[2], g.oz, g.inv_cell, g.nz);
-  if (!sweep_only) {   // shared overflow list (usually empty)
+  if (!sweep_only) {   // shared overflow list (usually empty), the wavefronts' batches in turn: knn_dev.h's ovf_scan(g, wv * 64,
+    // 256, ...) spelled out - through the helper two compares of this loop swap places in k_knn_grid_wg's stream
     int no = g.ovf_cnt[0];
     if (no > g.ovf_cap) no = g.ovf_cap;
     for (int base = wv * 64; base < no; base += 256) {
@@ -488,12 +449,9 @@ __device__ void knn_wg_search(const GridView& g, const NodeStoreView& st, const 
         const int c = (b0 + 4 * u + wv) * 64 + lane;
         cell[u] = 0; m[u] = 0;
         if (c < total) {
-          const int x = cx + c % w - r_first, y = cy + (c / w) % w - r_first, z = cz + c / (w * w) - r_first;
-          if (x >= 0 && x < g.nx && y >= 0 && y < g.ny && z >= 0 && z < g.nz) {
-            cell[u] = (z * g.ny + y) * g.nx + x;
-            m[u] = g.cnt[cell[u]];
-            if (m[u] > g.bk) m[u] = g.bk;
-          }
+          int x, y, z;
+          cube_cell(cx, cy, cz, r_first, c, x, y, z);
+          grid_cell_fill(g, g, x, y, z, cell[u], m[u]);
         }
       }
 #pragma unroll
@@ -501,16 +459,13 @@ __device__ void knn_wg_search(const GridView& g, const NodeStoreView& st, const 
         if (__any(m[u] > 0)) knn_cells(g, m[u], cell[u], lane, Q, st, t, k, have, false, 0.0, nullptr, n_mates, 0, bd, bi);
     }
     merge();
-    const int r = r_first;
-    const double covered = (double)r * cell_edge - slack;
-    done = (tree_nodes <= k && G >= tree_nodes) || (G >= k && bd <= covered) ||
-           (cx - r <= 0 && cy - r <= 0 && cz - r <= 0 && cx + r >= g.nx - 1 && cy + r >= g.ny - 1 && cz + r >= g.nz - 1);
+    done = (tree_nodes <= k && G >= tree_nodes) || (G >= k && bd <= shells_reach(r_first, cell_edge, slack)) ||
+           shells_cover_grid(g, cx, cy, cz, r_first);
     r_start = r_first + 1;
   }
   for (int r = r_start; r <= rmax && !done; ++r) {
-    const int w = 2 * r + 1;
-    const int ww = w * w, ring = 8 * r;
-    const int total = r > 0 ? 2 * ww + (w - 2) * ring : 1;
+    const Shell sh = shell_of(r);
+    const int total = r > 0 ? sh.cells : 1;
     if (n_store > 0 && scanned + total > 4LL * n_store + 4096) { sweep = true; break; }
     scanned += total;
     for (int b0 = 0; b0 * 64 < total; b0 += 16) {
@@ -521,23 +476,8 @@ __device__ void knn_wg_search(const GridView& g, const NodeStoreView& st, const 
         cell[u] = 0; m[u] = 0;
         if (c < total) {
           int ox, oy, oz;
-          if (c < 2 * ww) {
-            const int face = c >= ww ? 1 : 0, i = c - face * ww;
-            ox = i % w - r; oy = i / w - r; oz = face ? r : -r;
-          } else {
-            const int cc = c - 2 * ww;
-            const int layer = cc / ring, pp = cc - layer * ring;
-            const int side = pp / (2 * r), t_ = pp - side * 2 * r;
-            oz = -r + 1 + layer;
-            ox = side == 0 ? -r + t_ : side == 1 ? r : side == 2 ? r - t_ : -r;
-            oy = side == 0 ? -r : side == 1 ? -r + t_ : side == 2 ? r : r - t_;
-          }
-          const int x = cx + ox, y = cy + oy, z = cz + oz;
-          if (x >= 0 && x < g.nx && y >= 0 && y < g.ny && z >= 0 && z < g.nz) {
-            cell[u] = (z * g.ny + y) * g.nx + x;
-            m[u] = g.cnt[cell[u]];
-            if (m[u] > g.bk) m[u] = g.bk;
-          }
+          shell_cell(sh, c, ox, oy, oz);
+          grid_cell_fill(g, g, cx + ox, cy + oy, cz + oz, cell[u], m[u]);
         }
       }
 #pragma unroll
@@ -546,9 +486,8 @@ __device__ void knn_wg_search(const GridView& g, const NodeStoreView& st, const 
     }
     merge();
     if (tree_nodes <= k && G >= tree_nodes) break;          // (a tree with no more than k nodes: all of them are in)
-    const double covered = (double)r * cell_edge - slack;   // (cells are assigned from fp32 coordinates)
-    if (G >= k && bd <= covered) break;
-    if (cx - r <= 0 && cy - r <= 0 && cz - r <= 0 && cx + r >= g.nx - 1 && cy + r >= g.ny - 1 && cz + r >= g.nz - 1) break;
+    if (G >= k && bd <= shells_reach(r, cell_edge, slack)) break;
+    if (shells_cover_grid(g, cx, cy, cz, r)) break;
   }
   if (sweep) {   // (k_knn_linear's loop, 256 nodes per wavefront and trip; what the shells found is found again)
     t = TopK{1.0e300, 0x7fffffff};
@@ -620,14 +559,14 @@ __global__ __launch_bounds__(256) void k_knn_grid_wg(GridView g, NodeStoreView s
 // batches of cells in turn and merge their lists after every shell (knn_wg_search, the RRT session's k-nearest search) -
 // one lone wavefront per accepted sample was 44 us per sample on configs[4] and 80 for the tenth of them that walk shells,
 // and the launch is as long as its slowest sample.  Wave 0 then adds the round's earlier accepted samples and writes the
-// members and their toucher lists exactly as k_star_knn does.  Same keys: the same sets.
-#define SKW_MATE_U 16
+// members and their toucher lists through the very functions k_star_knn calls (knn_dev.h: star_earlier_samples,
+// star_publish).  Same keys: the same sets.
 #ifndef SKW_FIRST
 #define SKW_FIRST 1
 #endif
 __global__ __launch_bounds__(256) void k_star_knn_wg(ResolveArgs A, GridView g, GridView tg, NodeStoreView st, double cell_edge,
                                                      double slack, int R0) {
-  __shared__ int s_mate[64 * SKW_MATE_U];
+  __shared__ int s_mate[64 * STAR_MATE_U];
   const DevForestView& f = A.f;
   const StarView& S = A.S;
   const DevCtrl* c = f.ctrl;
@@ -636,26 +575,20 @@ __global__ __launch_bounds__(256) void k_star_knn_wg(ResolveArgs A, GridView g, 
   const int N0 = c->app_N0, Tb = f.temp_base;
   const unsigned ep = (unsigned)c->epoch;
   const int i_first = S.acc_sample[blockIdx.x];    // (asked for with the header words; the grid never exceeds the list's size)
-  if (blockIdx.x == 0 && threadIdx.x < SFFK_STAR_PASSES) S.changed[threadIdx.x] = 0;
-  if (blockIdx.x == 0 && threadIdx.x == 0) { S.changed[SFFK_STAR_BAR] = 0; S.hdr[STAR_PASSES_RUN] = 0; S.hdr[STAR_CONVERGED] = 0; }   // (k_star_tail)
-  for (int t = blockIdx.x * 256 + threadIdx.x; t < SFFK_STAR_PASSES * SFFK_SUBLISTS * SFFK_STAR_SUB; t += gridDim.x * 256) S.sub[t] = 0;
+  star_launch_reset(S);
   if (n <= 0) return;
   const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
   for (int r = blockIdx.x; r < n_acc; r += gridDim.x) {
     const int i = r == (int)blockIdx.x ? i_first : S.acc_sample[r];
     const unsigned long long dbg_t0 = S.dbg ? wall_clock64() : 0ULL;
-    // k = (size_t)(2e log10(#nodes)) with the nodes accepted before this sample counted in (src/forest.h:309)
-    const int Nn = N0 + r;
-    const int k_ref = __popcll(__ballot(lane > 0 && lane <= SFFK_STAR_KMAX + 1 && S.ktab[lane] <= Nn));
+    const int k_ref = star_k(S, N0 + r, lane);
     const int self = Tb + i;
     const int mine = st.tree[self];
     double qp[6];
     for (int q = 0; q < 6; ++q) qp[q] = A.newpos[6 * (size_t)i + q];
     // (wave 0: what the end needs, asked for beside the search - see k_star_knn)
-    int sidv[SKW_MATE_U], trv[SKW_MATE_U];
-    const bool mates_small = wave == 0 && r > 0 && r <= 64 * SKW_MATE_U;
-#pragma unroll
-    for (int u = 0; u < SKW_MATE_U; ++u) { const int rq = 64 * u + lane; sidv[u] = (mates_small && rq < r) ? Tb + S.acc_sample[rq] : -1; }
+    int sidv[STAR_MATE_U], trv[STAR_MATE_U];
+    star_earlier_ids(S, Tb, r, lane, wave == 0, sidv);
     const int ex0 = A.parent[i];
     const double pd0 = A.pdist[i];
     const int tcnt = S.tree_cnt[16 * mine];
@@ -664,12 +597,11 @@ __global__ __launch_bounds__(256) void k_star_knn_wg(ResolveArgs A, GridView g, 
       S.ew[s0] = 0; S.ew[s0 + 1] = 0;
     }
     if (k_ref > SFFK_STAR_KMAX) {   // (a node count beyond what the member slots are sized for: host path)
-      if (threadIdx.x == 0) atomicOr(S.hdr + 4, 1);
+      if (threadIdx.x == 0) atomicOr(S.hdr + STAR_FAULT, 1);
       continue;
     }
     const int k = k_ref;
-#pragma unroll
-    for (int u = 0; u < SKW_MATE_U; ++u) trv[u] = sidv[u] >= 0 ? st.tree[sidv[u]] : -1;
+    star_earlier_trees(st, sidv, trv);
     const double dr0 = f.d_root[ex0];
     TopK t{1.0e300, 0x7fffffff};
     int have = 0;
@@ -686,132 +618,15 @@ __global__ __launch_bounds__(256) void k_star_knn_wg(ResolveArgs A, GridView g, 
       const int cx = grid_coord((float)qp[0], g.ox, g.inv_cell, g.nx), cy = grid_coord((float)qp[1], g.oy, g.inv_cell, g.ny),
                 cz = grid_coord((float)qp[2], g.oz, g.inv_cell, g.nz);
       const int rmax = max(max(g.nx, g.ny), g.nz);
-      if (k > 0) {
-    // ---- the samples accepted earlier in this round (ranks below this one's, k_commit's list) of the same tree: not
-    // farther than the k-th store node - or, while the store holds fewer than k nodes of the tree, all of them
-    if (r > 0) {
-      const bool all = have < k;
-      const double limit = all ? 1.0e300 : topk_worst(t, k, have);
-      if (r <= 64 * SKW_MATE_U) {
-        // k_commit's list of the accepted samples: every rank's sample and tree are requested up front (two trips to
-        // memory whatever the length), the few of the same tree are compacted in LDS and measured a batch at a time
-        int* ml = s_mate;
-        int nm = 0;
-#pragma unroll
-        for (int u = 0; u < SKW_MATE_U; ++u) {
-          if (64 * u >= r) break;
-          const bool mt = sidv[u] >= 0 && trv[u] == mine;
-          const unsigned long long mm = __ballot(mt);
-          if (mt) ml[nm + __popcll(mm & ((1ULL << lane) - 1ULL))] = sidv[u];
-          nm += __popcll(mm);
-        }
-        __builtin_amdgcn_wave_barrier();
-        for (int base = 0; base < nm; base += 64) {
-          const int j = base + lane;
-          bool cand = false;
-          double d = 1.0e300;
-          int sid = 0x7fffffff;
-          if (j < nm) {
-            sid = ml[j];
-            double mp[6];
-            for (int q = 0; q < 6; ++q) mp[q] = st.pos[6 * (size_t)sid + q];
-            d = dist6(mp, qp);
-            cand = d <= limit;
-          }
-          const double worst = topk_worst(t, k, have);
-          cand = cand && (have < k || key_less(d, sid, worst, 0x7fffffff));
-          topk_insert(t, lane, k, have, __ballot(cand), d, sid);
-        }
-      } else if (all) {
-        for (int base = 0; base < r; base += 64) {   // (a tree wanted whole in a huge round: rare)
-          const int rq = base + lane;
-          bool cand = false;
-          double d = 1.0e300;
-          int sid = 0x7fffffff;
-          if (rq < r) {
-            sid = Tb + S.acc_sample[rq];
-            if (st.tree[sid] == mine) {
-              double mp[6];
-              for (int q = 0; q < 6; ++q) mp[q] = st.pos[6 * (size_t)sid + q];
-              d = dist6(mp, qp);
-              cand = true;
-            }
-          }
-          const double worst = topk_worst(t, k, have);
-          cand = cand && (have < k || key_less(d, sid, worst, 0x7fffffff));
-          topk_insert(t, lane, k, have, __ballot(cand), d, sid);
-        }
-      } else {
-        // a large round: the round's own grid, cells of the cube around the ball of the k-th store node
-        int rr = (int)((limit + slack) / cell_edge) + 1;
-        if (rr > rmax) rr = rmax;
-        const int w = 2 * rr + 1;
-        const int total = w * w * w;
-        for (int c0 = 0; c0 < total; c0 += 64) {
-          const int cc = c0 + lane;
-          int cell = 0, m = 0;
-          if (cc < total) {
-            const int x = cx + cc % w - rr, y = cy + (cc / w) % w - rr, z = cz + cc / (w * w) - rr;
-            if (x >= 0 && x < g.nx && y >= 0 && y < g.ny && z >= 0 && z < g.nz) {
-              cell = (z * g.ny + y) * g.nx + x;
-              const bool maybe = tg.occ ? ((tg.occ[cell >> 5] >> (cell & 31)) & 1u) != 0 : true;
-              if (maybe) { m = tg.cnt[cell]; if (m > tg.bk) m = tg.bk; }
-            }
-          }
-          if (__any(m > 0)) star_cells_mates(tg, m, cell, lane, qp, mine, Tb, self, limit, f, t, k, have);
-        }
-        int no = tg.ovf_cnt[0];
-        if (no > tg.ovf_cap) no = tg.ovf_cap;
-        for (int base = 0; base < no; base += 64) {
-          const int j = base + lane;
-          bool cand = false;
-          double d = 1.0e300;
-          int id = 0x7fffffff;
-          const double worst = topk_worst(t, k, have);
-          if (j < no) {
-            const GridItem it = tg.ovf[j];
-            id = it.id;
-            int rk;
-            if (it.tree == mine && id >= Tb && id < self && star_accepted(f, id - Tb, rk)) {
-              d = dist6(it.p, qp);
-              cand = d <= limit && (have < k || key_less(d, id, worst, 0x7fffffff));
-            }
-          }
-          topk_insert(t, lane, k, have, __ballot(cand), d, id);
-        }
+      if (k > 0)
+        star_earlier_samples(S, f, g, tg, st, qp, mine, Tb, self, r, sidv, trv, s_mate, cx, cy, cz, rmax, cell_edge, slack, lane, t, k, have);
+      if (S.dbg) dbg_t2 = wall_clock64();
+      star_publish(S, f, i, N0, Tb, ep, lane, t, have, ex0, pd0, dr0);
+      if (lane == 0 && S.dbg && k > 0) {   // SFFGPU_PROFILE: samples | ticks: search (four wavefronts), earlier samples, lists | longest sample
+        const unsigned long long t3 = wall_clock64();
+        atomicAdd(S.dbg + 0, 1ULL); atomicAdd(S.dbg + 1, dbg_t1 - dbg_t0); atomicAdd(S.dbg + 3, dbg_t2 - dbg_t1); atomicAdd(S.dbg + 4, t3 - dbg_t2);
+        atomicMax(S.dbg + 7, t3 - dbg_t0);
       }
-    }
-  }
-  if (S.dbg) dbg_t2 = wall_clock64();
-  // ---- the members: ids, distances, toucher lists
-  const int cnt = have;
-  const bool mem = lane < cnt;
-  int node = -1;
-  if (mem) {
-    if (t.id < N0) node = t.id;
-    else { int rk; star_accepted(f, t.id - Tb, rk); node = N0 + rk; }
-  }
-  const size_t p = (size_t)i * SFFK_STAR_KC + lane;
-  S.prop[p] = __longlong_as_double(0x7ff0000000000000LL);
-  if (mem) {
-    S.m_id[p] = node;
-    S.m_d[p] = t.d;
-    const unsigned long long mark = ((unsigned long long)ep << 32) | (unsigned long long)(p + 1);
-    const unsigned long long old = atomicExch(&S.head[node], mark);
-    S.next[p] = (unsigned)(old >> 32) == ep ? (int)(unsigned)(old & 0xffffffffULL) : 0;
-  }
-  if (lane == 0) {
-    S.m_cnt[i] = cnt;
-    S.best[i] = pd0 + dr0;   // (first guess: the plain SFF cost)
-    S.psel[i] = ex0;
-    S.dcl[i] = pd0;
-    S.cnt[2 * (size_t)i] = 0ULL; S.cnt[2 * (size_t)i + 1] = 0ULL;
-    if (S.dbg && k > 0) {   // SFFGPU_PROFILE: samples | ticks: search (four wavefronts), earlier samples, lists | longest sample
-      const unsigned long long t3 = wall_clock64();
-      atomicAdd(S.dbg + 0, 1ULL); atomicAdd(S.dbg + 1, dbg_t1 - dbg_t0); atomicAdd(S.dbg + 3, dbg_t2 - dbg_t1); atomicAdd(S.dbg + 4, t3 - dbg_t2);
-      atomicMax(S.dbg + 7, t3 - dbg_t0);
-    }
-    }
     }
     __syncthreads();   // (the search's LDS and s_mate are the next sample's)
   }

@@ -89,8 +89,8 @@ __device__ __forceinline__ void wt_u8(uint8_t* p, uint8_t v) { __hip_atomic_stor
 
 // ---- the idioms of the one-slot loops (seq_waves_body.inc, k_spec_waves, rrt_seq_batch.inc): ONE wavefront works for one
 // attempt, all 64 lanes together.  The round kernels and sq_knn keep their own copies of the flattening below
-// (qc_candidates, collect_from_grid, knn_cells, star_cells_mates ...): helpers cost time there, profiles/README.md
-// ("Shared idioms") has the numbers.
+// (qc_candidates, collect_from_grid ...): helpers cost time there, profiles/README.md ("Shared idioms") has the numbers;
+// the k-nearest kernels share theirs through knn_dev.h (lane_scan_incl, lane_owner).
 // fp32 half-edge of the cell box around an exact fp64 ball of radius r: the store's fp32 slack and a few ulps on top
 __device__ __forceinline__ float ball_box_radius(double r, double sweep_abs_eps) {
   const double ri = (r + sweep_abs_eps) * (1.0 + 1e-5);
@@ -316,8 +316,9 @@ __device__ __forceinline__ void surv_emit(SurvivorItem* buf, int& n_buf, bool le
   n_buf += total;
 }
 
-// ---- exact k nearest: the wave-resident top-k list shared by k_knn_linear / k_knn_grid (kernels.hip) and k_star_knn
-// (devstar.hip)
+// ---- exact k nearest: the wave-resident top-k list of k_knn_linear, the one-slot loops' sq_knn and the grid k-nearest
+// family (k_knn_grid, k_knn_grid_wg, k_star_knn_wg, k_star_knn), whose shared cell, lane and overflow idioms and SFF*
+// stages are knn_dev.h's
 // The wave's k best so far: lane j holds the j-th smallest (distance, id) key; lanes >= have hold +inf.
 struct TopK {
   double d;
@@ -393,44 +394,6 @@ __device__ __forceinline__ bool star_accepted(const DevForestView& f, int i, int
   const unsigned long long w = f.w_acc[i >> 6];
   rank = f.acc_pref[i >> 6] + __popcll(w & ((1ULL << (i & 63)) - 1ULL));
   return (w >> (i & 63)) & 1ULL;
-}
-
-// the same over cells of the round's own grid: samples accepted EARLIER in the round (temporary id in [Tb, self)) of
-// the same tree, not farther than `limit`
-__device__ __forceinline__ void star_cells_mates(const GridView& tg, int m, int cell, int lane, const double* qp, int tree, int Tb,
-                                                 int self, double limit, const DevForestView& f, TopK& t, int k, int& have) {
-  int inc = m;
-  for (int off = 1; off < 64; off <<= 1) {
-    const int o = __shfl_up(inc, off);
-    if (lane >= off) inc += o;
-  }
-  const int total = __shfl(inc, 63);
-  for (int base = 0; base < total; base += 64) {
-    const int j = base + lane;
-    const int jj = j < total ? j : total - 1;
-    int lo = 0, hi = 63;
-    while (lo < hi) {
-      const int mid = (lo + hi) >> 1;
-      if (__shfl(inc, mid) > jj) hi = mid; else lo = mid + 1;
-    }
-    const int src_cell = __shfl(cell, lo);
-    const int slot = jj - (__shfl(inc, lo) - __shfl(m, lo));
-    bool cand = false;
-    double d = 1.0e300;
-    int id = 0x7fffffff;
-    if (j < total) {
-      const GridItem it = tg.items[(size_t)src_cell * tg.bk + slot];
-      id = it.id;
-      int rk;
-      if (it.tree == tree && id >= Tb && id < self && star_accepted(f, id - Tb, rk)) {
-        d = sffg::dist6(it.p, qp);
-        cand = d <= limit;
-      }
-    }
-    const double worst = topk_worst(t, k, have);
-    cand = cand && (have < k || key_less(d, id, worst, 0x7fffffff));
-    topk_insert(t, lane, k, have, __ballot(cand), d, id);
-  }
 }
 
 
