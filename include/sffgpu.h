@@ -282,6 +282,37 @@ typedef struct {
 int sffgpu_forest_smooth_paths_batch(sffgpu_forest* const* f, int n, double* const* dist /* n pointers, each may be NULL */,
                                      int32_t* failed /* may be NULL */);
 int sffgpu_forest_get_smooth_stats(sffgpu_forest* f, sffgpu_smooth_stats* out);
+/* Path extraction for n forests together: every member ends exactly as its own sffgpu_forest_paths leaves it - the matrix
+ * (node ids, costs bit for bit, plans), connectedTrees and its order, what sffgpu_forest_path_plan and
+ * sffgpu_forest_get_borders report afterwards.  A member whose state lives on the device (grown by the device engine or a
+ * forest batch and not downloaded since, between two waves, at most 64 trees) has it done there, by k_paths_batch: one
+ * workgroup per member, ONE launch for all of them, and only the plans and the fp64 positions of their entries come down -
+ * the forest itself is not downloaded, neither here nor by a following sffgpu_forest_smooth_paths_batch; the first getter
+ * that needs the forest (nodes, borders, fingerprint, frontier, sffgpu_forest_smooth_paths' host walk) downloads it as
+ * before.  Every other member takes sffgpu_forest_paths' own route inside the call, so any forest is accepted; so does a
+ * member whose plans outgrow its pool on the device (8192 plan entries; sffgpu_paths_stats::fallbacks).
+ * dist: n pointers, each NULL or room for that forest's n_trees x n_trees matrix; connected: NULL, or n pointers, each NULL
+ * or room for n_trees ids; n_connected: NULL or n counts.  Arguments and errors are sffgpu_forest_smooth_paths_batch's:
+ * SFFGPU_ERR_ARG for n <= 0, NULL, a NULL member, the same forest twice or members on different devices; if a member fails,
+ * *failed = its index (-1 otherwise), the message is on ITS context and no member's matrix or connectedTrees has been
+ * touched.  A forest created under SFFGPU_PATHS_DEV=1 takes this path (n = 1) in sffgpu_forest_paths too. */
+int sffgpu_forest_paths_batch(sffgpu_forest* const* f, int n,
+                              double* const* dist,          /* n pointers, each NULL or n_trees x n_trees */
+                              int32_t* const* connected,    /* n pointers, each NULL or room for n_trees; may itself be NULL */
+                              int32_t* n_connected,         /* n counts; may be NULL */
+                              int32_t* failed               /* may be NULL */);
+typedef struct {
+  uint64_t calls;        /* calls this forest took part in (a knob-routed single call included) */
+  uint64_t launches;     /* launches of the kernel it took part in */
+  uint64_t device_calls; /* calls that extracted its paths on the device */
+  uint64_t host_calls;   /* calls that took the host route from the start */
+  uint64_t fallbacks;    /* calls in which the device route gave up (plan pool full) and the host route finished */
+  uint64_t host_syncs;   /* calls that downloaded the forest (Forest::sync_host did work) */
+  uint64_t pairs;        /* pairs with a path after the last call */
+  uint64_t entries;      /* plan entries brought down, all calls */
+  double ms;             /* wall time of the calls */
+} sffgpu_paths_stats;
+int sffgpu_forest_get_paths_stats(sffgpu_forest* f, sffgpu_paths_stats* out);
 
 /* ---------------------------------------------------------------- RRT / RRT* / Multi-T-RRT
  * RapidExpTree<T,R> (src/rrt.h:25-44): constructor :47-83, Solve() :86-99, expandNode :128-322

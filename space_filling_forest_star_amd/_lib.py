@@ -26,6 +26,7 @@ EXPORTED_SYMBOLS = [
     "sffgpu_forest_run_batch", "sffgpu_rrt_run_batch",
     "sffgpu_forest_smooth_paths_batch", "sffgpu_rrt_smooth_paths_batch", "sffgpu_forest_get_smooth_stats",
     "sffgpu_rrt_get_smooth_stats",
+    "sffgpu_forest_paths_batch", "sffgpu_forest_get_paths_stats",
     "sffgpu_create_member", "sffgpu_ctx_get_memory", "sffgpu_ctx_grid_compact",
 ]
 
@@ -91,6 +92,16 @@ class SmoothStats(C.Structure):
     """sffgpu_smooth_stats: what the device loop of path smoothing (k_smooth_paths) has done for one planner"""
     _fields_ = [("launches", C.c_uint64), ("paths", C.c_uint64), ("steps", C.c_uint64), ("edges", C.c_uint64),
                 ("host_edges", C.c_uint64), ("ms", C.c_double)]
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_}
+
+
+class PathsStats(C.Structure):
+    """sffgpu_paths_stats: what path extraction for forests together (paths_batch, k_paths_batch) has done for one forest"""
+    _fields_ = [("calls", C.c_uint64), ("launches", C.c_uint64), ("device_calls", C.c_uint64), ("host_calls", C.c_uint64),
+                ("fallbacks", C.c_uint64), ("host_syncs", C.c_uint64), ("pairs", C.c_uint64), ("entries", C.c_uint64),
+                ("ms", C.c_double)]
 
     def as_dict(self):
         return {k: getattr(self, k) for k, _ in self._fields_}
@@ -180,6 +191,9 @@ def lib():
         L.sffgpu_rrt_smooth_paths_batch.argtypes = [C.POINTER(C.c_void_p), C.c_int, c_ip]
         L.sffgpu_forest_get_smooth_stats.argtypes = [C.c_void_p, C.POINTER(SmoothStats)]
         L.sffgpu_rrt_get_smooth_stats.argtypes = [C.c_void_p, C.POINTER(SmoothStats)]
+    if hasattr(L, "sffgpu_forest_paths_batch"):   # (SFFGPU_LIB may name a build from before path extraction on the device)
+        L.sffgpu_forest_paths_batch.argtypes = [C.POINTER(C.c_void_p), C.c_int, C.POINTER(c_dp), C.POINTER(c_ip), c_ip, c_ip]
+        L.sffgpu_forest_get_paths_stats.argtypes = [C.c_void_p, C.POINTER(PathsStats)]
     L.sffgpu_rrt_get_nodes.argtypes = [C.c_void_p, c_dp, c_ip, c_ip, c_ip, c_ip, c_dp, c_dp]
     L.sffgpu_rrt_get_links.argtypes = [C.c_void_p, c_ip, c_ip, c_ip, c_dp, C.c_int]
     L.sffgpu_rrt_paths.argtypes = [C.c_void_p, c_dp, c_ip, C.c_int]
@@ -522,6 +536,13 @@ class Forest:
         under SFFGPU_SMOOTH_LOOP=1); launches == 0: it never ran"""
         s = SmoothStats()
         self.ctx._chk(self.ctx._L.sffgpu_forest_get_smooth_stats(self.h, C.byref(s)))
+        return s.as_dict()
+
+    def paths_stats(self):
+        """what paths_batch (or paths() of a forest created under SFFGPU_PATHS_DEV=1) has done for this forest; calls == 0:
+        it never ran"""
+        s = PathsStats()
+        self.ctx._chk(self.ctx._L.sffgpu_forest_get_paths_stats(self.h, C.byref(s)))
         return s.as_dict()
 
     def plan(self, i, j, cap=1 << 16):
@@ -932,6 +953,37 @@ def _smooth_error(L, rc, failed, members, what):
     elif rc == -1:
         msg += ": not a smoothing batch (needs n >= 1 %s, none of them twice, all on one device)" % what
     return SffGpuError(msg)
+
+
+def paths_batch(forests):
+    """getPaths + getAllPaths for independent forests together (sffgpu_forest_paths_batch): a forest whose state lives on the
+    device has its paths extracted there - one workgroup per forest, one kernel launch for all of them, only the plans and
+    their entries' positions come down -, every other forest takes paths()' own route inside the call; each forest ends
+    exactly as its own paths() would leave it.  All on one device.  Returns the list of (cost matrix, connected tree ids).
+    An error names the member it came from, and no member's paths have been touched."""
+    forests = list(forests)
+    L = lib()
+    if not hasattr(L, "sffgpu_forest_paths_batch"):
+        raise SffGpuError("this build of libsffgpu.so has no sffgpu_forest_paths_batch")
+    arr = (C.c_void_p * max(1, len(forests)))(*[getattr(f, "h", None) for f in forests])
+    mats, conns = [], []
+    for f in forests:
+        n = f.stats()["n_trees"] if getattr(f, "h", None) else 0
+        mats.append(np.zeros((n, n)))
+        conns.append(np.zeros(max(1, n), np.int32))
+    dist = (c_dp * max(1, len(forests)))(*[_dp(d) for d in mats])
+    conn = (c_ip * max(1, len(forests)))(*[_ip(c) for c in conns])
+    counts = np.zeros(max(1, len(forests)), np.int32)
+    failed = C.c_int32(-1)
+    rc = L.sffgpu_forest_paths_batch(arr if forests else None, len(forests), dist, conn, _ip(counts), C.byref(failed))
+    if rc < 0:
+        msg = "sffgpu error %d" % rc
+        if 0 <= failed.value < len(forests):
+            msg += " (member %d): %s" % (failed.value, L.sffgpu_last_error(forests[failed.value].ctx.h).decode())
+        elif rc == -1:
+            msg += ": not a paths batch (needs n >= 1 forests, none of them twice, all on one device)"
+        raise SffGpuError(msg)
+    return [(d, c[:k].copy()) for d, c, k in zip(mats, conns, counts)]
 
 
 def smooth_batch(forests):

@@ -141,6 +141,34 @@ static int smooth_ready(sffgpu_rrt* r) {
   r->owner->c->err = "rrt smooth_paths: call sffgpu_rrt_paths first";
   return SFFGPU_ERR_STATE;
 }
+// sffgpu_forest_paths_batch: smooth_batch_entry's argument rules; run_paths_batch decides every member's route
+static int paths_batch_entry(sffgpu_forest* const* h, int n, int32_t* failed) {
+  if (failed) *failed = -1;
+  if (!h || n <= 0) return SFFGPU_ERR_ARG;
+  std::vector<Forest*> members((size_t)n);
+  for (int i = 0; i < n; ++i) {
+    if (!h[i] || h[i]->f->ctx->device != h[0]->f->ctx->device) return SFFGPU_ERR_ARG;
+    for (int j = 0; j < i; ++j)
+      if (h[j] == h[i]) return SFFGPU_ERR_ARG;
+    members[(size_t)i] = h[i]->f;
+  }
+  int bad = -1;
+  auto blame = [&](const std::string& msg) {
+    if (bad < 0) bad = 0;
+    h[bad]->owner->c->err = msg;
+    if (failed) *failed = bad;
+  };
+  try {
+    run_paths_batch(members.data(), n, &bad);
+  } catch (const HipError& e) {
+    blame(e.msg);
+    return SFFGPU_ERR_HIP;
+  } catch (const std::exception& e) {
+    blame(e.what());
+    return SFFGPU_ERR_STATE;
+  }
+  return SFFGPU_OK;
+}
 static void copy_dist(Forest& F, double* dist) {
   for (int i = 0; i < F.num_roots; ++i)
     for (int j = 0; j < F.num_roots; ++j) dist[(size_t)i * F.num_roots + j] = i == j ? 0.0 : F.NM(i, j).dist;
@@ -374,6 +402,14 @@ uint64_t sffgpu_forest_fingerprint(sffgpu_forest* f) {
 int sffgpu_forest_paths(sffgpu_forest* f, double* dist, int32_t* connected, int cap_connected) {
   if (!f || !dist) return SFFGPU_ERR_ARG;
   Forest& F = *f->f;
+  if (F.kn.paths_dev) {   // (SFFGPU_PATHS_DEV=1 at the forest's creation: a batch of one)
+    const int rc = paths_batch_entry(&f, 1, nullptr);
+    if (rc != SFFGPU_OK) return rc;
+    copy_dist(F, dist);
+    if (connected)
+      for (size_t k = 0; k < F.connected.size() && (int)k < cap_connected; ++k) connected[k] = F.connected[k];
+    return (int)F.connected.size();
+  }
   try { F.sync_host(); } catch (const HipError& e) { f->owner->c->err = e.msg; return SFFGPU_ERR_HIP; }
   F.max_connected();                 // Solver::connectedTrees as Solve() leaves it (src/forest.h:196-206)
   F.get_paths();
@@ -393,6 +429,7 @@ int sffgpu_forest_smooth_paths(sffgpu_forest* f, double* dist) {
     return sffgpu_forest_smooth_paths_batch(&f, 1, one, nullptr);
   }
   GUARD(f->owner, {
+    F.sync_host();   // (the host walk reads the mirror; a no-op unless sffgpu_forest_paths_batch left it behind)
     F.smooth_paths();
     for (int i = 0; i < F.num_roots; ++i)
       for (int j = 0; j < F.num_roots; ++j) dist[(size_t)i * F.num_roots + j] = i == j ? 0.0 : F.NM(i, j).dist;
@@ -403,6 +440,24 @@ int sffgpu_forest_smooth_paths_batch(sffgpu_forest* const* f, int n, double* con
   if (rc == SFFGPU_OK && dist)
     for (int i = 0; i < n; ++i) if (dist[i]) copy_dist(*f[i]->f, dist[i]);
   return rc;
+}
+int sffgpu_forest_paths_batch(sffgpu_forest* const* f, int n, double* const* dist, int32_t* const* connected, int32_t* n_connected,
+                              int32_t* failed) {
+  const int rc = paths_batch_entry(f, n, failed);
+  if (rc != SFFGPU_OK) return rc;
+  for (int i = 0; i < n; ++i) {
+    Forest& F = *f[i]->f;
+    if (dist && dist[i]) copy_dist(F, dist[i]);
+    if (connected && connected[i])
+      for (size_t k = 0; k < F.connected.size(); ++k) connected[i][k] = F.connected[k];
+    if (n_connected) n_connected[i] = (int32_t)F.connected.size();
+  }
+  return rc;
+}
+int sffgpu_forest_get_paths_stats(sffgpu_forest* f, sffgpu_paths_stats* out) {
+  if (!f || !out) return SFFGPU_ERR_ARG;
+  *out = f->f->ps;
+  return SFFGPU_OK;
 }
 int sffgpu_forest_get_smooth_stats(sffgpu_forest* f, sffgpu_smooth_stats* out) {
   if (!f || !out) return SFFGPU_ERR_ARG;

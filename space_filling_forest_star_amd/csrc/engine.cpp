@@ -266,11 +266,11 @@ Ctx::~Ctx() {
                     &d_a, &d_b, &d_c, &d_d, &d_e, &d_f, &d_g, &d_h, &r_in, &r_out, &r_out2, &r_q, &r_cnt,
                     &r_sega, &r_segb, &r_items, &r_items2, &r_center, &r_qrec, &g_cnt, &g_items, &g_ovfcnt, &g_ovf, &g_bucket, &t_cnt, &t_items, &t_ovfcnt, &t_ovf, &t_occ, &g_lite, &g_ovf_lite, &t_lite, &t_ovf_lite, &r_sub, &rr_q1, &rr_q2, &rr_a, &rr_out, &rr_sq, &rr_np, &rr_alt, &rr_q2b, &rr_sqb, &seg_job[0].ids, &seg_job[0].a, &seg_job[0].b, &seg_job[0].c, &seg_job[1].ids, &seg_job[1].a,
                     &seg_job[1].b, &seg_job[1].c, &seg_job[2].ids, &seg_job[2].a, &seg_job[2].b, &seg_job[2].c, &seg_job[3].ids, &seg_job[3].a,
-                    &seg_job[3].b, &seg_job[3].c, &sm_dev};
+                    &seg_job[3].b, &seg_job[3].c, &sm_dev, &pp_dev};
   for (DevBuf* b : bufs) b->release();
   env.reset();   // (the models go with their last holder)
   PinBuf* pins[] = {&h_a, &h_b, &h_c, &h_d, &h_e, &h_f, &h_g, &h_h, &p_in, &p_out, &rr_hq, &rr_hout, &seg_job[0].hids, &seg_job[0].hc, &seg_job[1].hids, &seg_job[1].hc, &seg_job[2].hids, &seg_job[2].hc,
-                    &seg_job[3].hids, &seg_job[3].hc, &sm_pin};
+                    &seg_job[3].hids, &seg_job[3].hc, &sm_pin, &pp_pin};
   for (PinBuf* b : pins) b->release();
   if (copy_stream) (void)hipStreamDestroy(copy_stream);
   if (own_stream) (void)hipStreamDestroy(own_stream);
@@ -845,7 +845,7 @@ void Ctx::memory(sffgpu_ctx_memory* out) const {
   out->store_bytes = sum({&sx, &sy, &sz, &syaw, &spitch, &sroll, &stree, &spos});
   out->grid_bytes = sum({&g_cnt, &g_items, &g_ovfcnt, &g_ovf, &g_lite, &g_ovf_lite, &t_ovfcnt, &g_bucket});
   out->round_grid_bytes = sum({&t_cnt, &t_items, &t_ovf, &t_occ, &t_lite, &t_ovf_lite});
-  out->other_bytes = sum({&d_a, &d_b, &d_c, &d_d, &d_e, &d_f, &d_g, &d_h, &sm_dev, &r_in, &r_out, &r_q, &r_cnt, &r_sega, &r_segb,
+  out->other_bytes = sum({&d_a, &d_b, &d_c, &d_d, &d_e, &d_f, &d_g, &d_h, &sm_dev, &pp_dev, &r_in, &r_out, &r_q, &r_cnt, &r_sega, &r_segb,
                           &r_items, &r_items2, &r_sub, &r_center, &r_qrec, &r_out2, &rr_q1, &rr_q2, &rr_a, &rr_out, &rr_sq, &rr_np, &rr_alt, &rr_q2b, &rr_sqb});
   for (const SegJob& J : seg_job) out->other_bytes += sum({&J.ids, &J.a, &J.b, &J.c});
   out->total_bytes = out->env_bytes + out->store_bytes + out->grid_bytes + out->round_grid_bytes + out->other_bytes;

@@ -6,9 +6,11 @@
 #include <string.h>
 
 #include <algorithm>
+#include <array>
 #include <functional>
 #include <map>
 #include <memory>
+#include <unordered_map>
 #include <unordered_set>
 #include <string>
 #include <utility>
@@ -217,6 +219,8 @@ struct Ctx {
   PinBuf h_a, h_b, h_c, h_d, h_e, h_f, h_g, h_h;
   DevBuf sm_dev;   // path smoothing on the device (smooth_batch.cpp): path table | control blocks | output rows | positions,
   PinBuf sm_pin;   // of the call whose first member this context belongs to, and their pinned image
+  DevBuf pp_dev;   // path extraction on the device (paths_batch.cpp): member arguments | answer headers, then gather parts |
+  PinBuf pp_pin;   // packed answers, of the call whose first device-route member this context belongs to, and their pinned image
   // round pipeline buffers of the forest engine (kept apart from the batch entry points' scratch)
   DevBuf r_in, r_out, r_q, r_cnt, r_sega, r_segb, r_items, r_items2, r_sub, r_center;
   DevBuf r_qrec;   // per sample: QRec (kernels.h), written by the sampling kernels for k_query_block
@@ -579,6 +583,17 @@ struct Forest {
   void get_all_paths();
   void smooth_paths();   // src/forest.h:464-511, edge checks batched on the GPU
   sffgpu_smooth_stats sm{};   // what the device loop (smooth_batch.cpp) has done for this forest; all zero = it never ran
+  // path extraction on the device (paths_batch.cpp / devpaths.hip): the forest's working rows, plan pool and packed answer,
+  // allocated by its first call; cap = plan entries of the pool (8192, or SFFGPU_TEST_PATHS_CAP at the forest's creation)
+  struct PathsDev { DevBuf rows, pool, packed; int cap = 0; } pd;
+  sffgpu_paths_stats ps{};    // what sffgpu_forest_paths_batch has done for this forest; all zero = it never ran
+  // the fp64 positions that came down with the plans, by node id: what path smoothing reads while the mirror is behind
+  std::unordered_map<int, std::array<double, 6>> pos_cache;
+  // isPathFree / Collide calls made for this forest while the device held its counters (path smoothing of a forest that has
+  // not been downloaded): added wherever the device's figures become the forest's (fill_stats, sync_host), folded into the
+  // device's own when the state goes up again (dev_upload_state)
+  uint64_t post_path_free = 0, post_collide = 0;
+  const double* node_pos(int id) const;   // the mirror's where it holds the node (a position never changes), else the cache's; null = neither
 
   Forest(Ctx* c, const sffgpu_forest_cfg& cf, const double* roots6, int n_roots);
   int add_node(const double* pos, int tree, int parent, double dclosest, double droot, unsigned it);
@@ -692,6 +707,14 @@ struct Rrt {
 // session only when it was created under SFFGPU_LAZY_BATCH=1; distinct contexts, one device).  A member that throws ends the call: *failed = its index, the
 // exception goes on to the caller; every other member has been taken in after a whole number of launches.
 void run_rrt_batch(Rrt* const* members, int n, int max_iterations, int* failed);
+
+// Path extraction of n forests together (paths_batch.cpp): a member whose state is device-resident and ahead of the host
+// mirror, between two waves, with at most 64 trees, has its getPaths + getAllPaths done by k_paths_batch (devpaths.hip) - one
+// launch for all such members, a header copy, a gather launch, one copy of the packed plans and their entries' positions;
+// every other member, and one whose plan pool ran out, goes through sync_host + max_connected + get_paths + get_all_paths.
+// Nothing of a forest's nm / connected is touched before every member's answer is on the host: a member that throws ends
+// the call with *failed = its index.  The caller has checked the members (one device, distinct handles).
+void run_paths_batch(Forest* const* members, int n, int* failed);
 
 // Path smoothing on the device (smooth_batch.cpp): smoothPaths' walk for every path of n planners in one launch of
 // k_smooth_paths, one wavefront per path, launched again until every path is done (a launch tests at most max_edges edges

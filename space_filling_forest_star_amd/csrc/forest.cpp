@@ -257,8 +257,8 @@ void Forest::fill_stats(sffgpu_forest_stats* out) {
     s.closed_size = k.closed_n;
     s.n_connected = (int)conn.size();
     s.n_borders = k.n_borders;
-    s.collide_calls = k.collide_calls;
-    s.path_free_calls = k.path_free_calls;
+    s.collide_calls = k.collide_calls + post_collide;
+    s.path_free_calls = k.path_free_calls + post_path_free;
     s.nn_queries = k.nn_queries;
     s.poses_executed = k.poses_executed;
     s.segments_executed = k.segments_executed;
@@ -314,7 +314,7 @@ Forest::~Forest() {
                     &dev.s_evd, &dev.s_acc, &dev.s_backup, &dev.s_items, &dev.s_dbg, &dev.s_hist, &dev.w_acc, &dev.acc_pref, &dev.ustate32, &dev.wg_pub, &dev.commit_seq, &dev.kc_trace, &x_send, &x_recv,
                     &dev.hp_base, &dev.hp_size, &dev.hp_v, &dev.hp_key, &dev.hp_pos, &dev.hp_ref, &dev.hp_gen, &dev.hp_cnt, &dev.slot_tree, &dev.slot_heap, &dev.slot_idx, &dev.slot_word, &dev.hp_plan,
                     &dev.ord_hist, &dev.ord_start, &dev.ord_key, &dev.ord_rank, &dev.ord_pos, &dev.ord_lst, &dev.ord_cnt,
-                    &dev.w_ev, &dev.ev_h, &dev.ev_nb, &dev.ev_raw, &dev.spec_tab, &dev.spec_area, &dev.qclk_sh, &dev.seq_args};
+                    &dev.w_ev, &dev.ev_h, &dev.ev_nb, &dev.ev_raw, &dev.spec_tab, &dev.spec_area, &dev.qclk_sh, &dev.seq_args, &pd.rows, &pd.pool, &pd.packed};
   if (dev.inited) {
     (void)hipSetDevice(ctx->device);
     (void)hipStreamSynchronize(ctx->stream);

@@ -616,6 +616,7 @@ void Forest::dev_upload_state() {
     k.cursor = cursor;
     k.collide_calls = st.collide_calls;
     k.path_free_calls = st.path_free_calls;
+    post_collide = post_path_free = 0;   // (st holds them: the device counts on from the sum)
     k.nn_queries = st.nn_queries;
     k.poses_executed = st.poses_executed;
     k.segments_executed = st.segments_executed;
@@ -750,8 +751,8 @@ void Forest::sync_host() {
   empty_frontier = k.empty_frontier != 0;
   in_wave = k.in_wave != 0;
   round = k.round;
-  st.collide_calls = k.collide_calls;
-  st.path_free_calls = k.path_free_calls;
+  st.collide_calls = k.collide_calls + post_collide;
+  st.path_free_calls = k.path_free_calls + post_path_free;
   st.nn_queries = k.nn_queries;
   st.poses_executed = k.poses_executed;
   st.segments_executed = k.segments_executed;

@@ -105,6 +105,9 @@ Knobs Knobs::from_env() {
 
   k.smooth_loop = flag("SFFGPU_SMOOTH_LOOP", k.smooth_loop);
   k.smooth_edges = int_in("SFFGPU_SMOOTH_EDGES", k.smooth_edges, 1);
+
+  k.paths_dev = flag("SFFGPU_PATHS_DEV", k.paths_dev);
+  k.test_paths_cap = int_in("SFFGPU_TEST_PATHS_CAP", k.test_paths_cap, 1, 1 << 24);
   return k;
 }
 

@@ -101,6 +101,11 @@ struct Knobs {
                                     // paths on the device (k_smooth_paths, the batch runner with one member); 0 = the host walk, one edge batch per step
   int smooth_edges = 64;            // SFFGPU_SMOOTH_EDGES (>= 1): most edges one launch of k_smooth_paths tests per path before the host launches again
 
+  // ---- path extraction (forests)
+  bool paths_dev = false;           // SFFGPU_PATHS_DEV=1: sffgpu_forest_paths of a forest created under it is sffgpu_forest_paths_batch with one member
+                                    // (k_paths_batch where the forest's state is on the device); 0 = sync_host + the host's getPaths / getAllPaths
+  int test_paths_cap = 0;           // SFFGPU_TEST_PATHS_CAP=n (>= 1), tests: plan entries of the forest's pool on the device (0 = unset: 8192)
+
   static Knobs from_env();
 };
 

@@ -5,6 +5,8 @@
 // Solver::getAllPaths (src/problemStruct.h:184-253) closes the matrix over the connected trees by
 // joining paths that share a third tree.  Costs feed params.csv / the TSP file
 // (src/problemStruct.h:391-468); they are the "path cost" the parity bound is stated on.
+// The same two steps for the forests of a batch whose state lives on the device: devpaths.hip (k_paths_batch), paths_batch.cpp;
+// the border pick and the join are stated once more, for kernel and host, in paths_rules.h.
 #include <algorithm>
 #include <cmath>
 #include <cstring>

@@ -2,7 +2,8 @@
 // smooth_paths.inc), one wavefront per path, and what each planner makes of the answer.  engine.h says what a member is.
 //
 // A call: every member's stream is drained; the fp64 positions of every plan entry are gathered from the members' host
-// mirrors (sffgpu_forest_paths / sffgpu_rrt_paths have synced them) and go up with the path table and the control blocks as
+// mirrors (sffgpu_forest_paths / sffgpu_rrt_paths have synced them) or, behind sffgpu_forest_paths_batch's device route,
+// from the positions that came down with the plans, and go up with the path table and the control blocks as
 // ONE copy; one launch on the first member's stream, the control blocks and output rows back as ONE copy, one wait; again
 // while a path is unfinished (a launch tests at most Knobs::smooth_edges edges of a path).  A step the kernel hands over
 // (SFFK_SMOOTH_HOST) is finished here through the member's Ctx::collide_segments.  Only when every path of every member is
@@ -183,8 +184,10 @@ SmoothMember smooth_member(Forest& f) {
   m.ctx = f.ctx;
   m.max_edges = f.kn.smooth_edges;
   m.stats = &f.sm;
-  m.path_free_calls = &f.st.path_free_calls;
-  m.collide_calls = &f.st.collide_calls;
+  // (while the device holds the forest's counters - paths extracted there, nothing downloaded - st is not what the getters read)
+  const bool behind = f.dev.active && f.dev.host_stale;
+  m.path_free_calls = behind ? &f.post_path_free : &f.st.path_free_calls;
+  m.collide_calls = behind ? &f.post_collide : &f.st.collide_calls;
   std::vector<Forest::Holder*> holders;
   for (int i = 0; i < f.num_roots; ++i)
     for (int j = i + 1; j < f.num_roots; ++j) {
@@ -194,11 +197,16 @@ SmoothMember smooth_member(Forest& f) {
       m.plans.push_back(&h.plan);
     }
   Forest* F = &f;
-  m.pos = [F](int node) { return F->nodes[(size_t)node].pos; };
+  // (positions through the forest's accessor: the mirror's, or - after sffgpu_forest_paths_batch took the device route and
+  // nothing has been downloaded since - the ones that came down with the plans)
+  m.pos = [F](int node) {
+    const double* p = F->node_pos(node);
+    if (!p) throw HipError{"smooth_paths: the position of a plan entry is not on the host"};
+    return p;
+  };
   m.apply = [F, holders](int path, const int32_t* ts, int n_ts) {
     Forest::Holder& h = *holders[(size_t)path];
     std::vector<int>& plan = h.plan;
-    const std::vector<FNode>& nodes = F->nodes;
     int g = (int)plan.size() - 1, k = 0;
     double prev_dist = h.dist;
     while (g > 0 && k < n_ts) {
@@ -207,14 +215,14 @@ SmoothMember smooth_member(Forest& f) {
       double cum = 0;
       bool changed = false;
       while (t < g - 1) {
-        if (p != t) cum += sffg::dist6(nodes[plan[t]].pos, nodes[plan[p]].pos);
+        if (p != t) cum += sffg::dist6(F->node_pos(plan[t]), F->node_pos(plan[p]));
         if (t == chosen) { changed = true; break; }
         p = t;
         ++t;
       }
-      if (t == g - 1) cum += sffg::dist6(nodes[plan[t]].pos, nodes[plan[p]].pos);
+      if (t == g - 1) cum += sffg::dist6(F->node_pos(plan[t]), F->node_pos(plan[p]));
       if (changed) {
-        double dif = prev_dist - cum - sffg::dist6(nodes[plan[t]].pos, nodes[plan[g]].pos);
+        double dif = prev_dist - cum - sffg::dist6(F->node_pos(plan[t]), F->node_pos(plan[g]));
         h.dist -= dif;
         plan.erase(plan.begin() + t + 1, plan.begin() + g);
       }
